@@ -16,10 +16,17 @@ over RCCL once per iteration.  Two launch forms, same library path (csrc/comm.cp
     ncclCommInitAll (what `BaMMmotif --gpus N` and integration/sharded_em.cpp do).  Fewer visible
     devices than N is an error, never a silent single-GPU run.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with two extra objects:
+Prints ONE JSON line on rank 0 (contract in the task statement) with extra objects:
   roofline     algorithmic HBM bytes of the sequence kernel / its HIP-event duration vs 8 TB/s
   cpu_baseline the reference's own EM (oracle/_ref, OpenMP) timed on the host cores on a
-               bounded sample of the same workload (rank 0, N = 1 only)
+               bounded sample of the same workload (rank 0, N = 1 only; --full)
+  from_seed    the first passes from the seed as iterate() and optimize(), and the first handle
+               of the process (N = 1 only; --full)
+
+A plain run sets up, warms up, times --steps passes and prints the line; --full adds the figures
+beside it.  --dump-outputs DIR writes what the timed call left in its handle (the model, the last
+M-step's counts, the per-pass trace) as float32 .npy files, so that two builds can be compared
+output for output on the same seeded workload.
 """
 from __future__ import annotations
 
@@ -36,6 +43,7 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0          # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E 8 TB/s (spec)
+DUMP_CAP_WORDS = 4 << 20       # --dump-outputs: at most 16 MB per array, 64 MB for the four
 
 
 def algorithmic_bytes(positions: int, windows: int, sliced: bool) -> float:
@@ -72,6 +80,12 @@ def parse():
     ap.add_argument("--torch-allreduce", action="store_true",
                     help="all-reduce through torch.distributed.all_reduce from a Python callback instead of the "
                          "library's own RCCL call (bamm_em_set_comm), which is the default with the nccl backend")
+    ap.add_argument("--full", action="store_true",
+                    help="also the figures beside the headline, each with runs of its own: the CPU baseline and, on one GPU, the "
+                         "cold-start / optimize()-mode figures (--no-cpu-baseline / --no-extras leave them out again)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed region: the model v, the last M-step's counts and the per-pass llh / v_diff trace of "
+                         "the timed handle as DIR/<name>.npy (float32, rank 0)")
     ap.add_argument("--no-extras", action="store_true", help="skip the cold-start / optimize()-mode figures")
     ap.add_argument("--local-ranks", action="store_true",
                     help="in-process form only: --gpus N ranks as N contexts on device 0 with the host-staged sum of "
@@ -309,7 +323,7 @@ def report(args, wl, world, dt, kernel_ms, launches, local_positions, local_wind
         "iterations_per_s": its,
         "windows_per_s": total_windows * its,
         "timed_region": f"passes {args.warmup + 1}-{args.warmup + args.steps} of one handle through iterate() (fixed budget, SURVEY H5); "
-                        "`from_seed` beside it: the first passes from the seed model, as iterate() and as optimize()",
+                        "`from_seed` beside it (--full): the first passes from the seed model, as iterate() and as optimize()",
         "config": {"workload": f"{args.nseq}x{L0}bp {'single' if args.ss else 'double'}-strand "
                                f"(L={L}), W={W}, k={K}, K_bg=2, --EM, fixed iteration budget",
                    "n_seqs": args.nseq, "seq_len": L0, "W": W, "k": K,
@@ -357,7 +371,7 @@ def report(args, wl, world, dt, kernel_ms, launches, local_positions, local_wind
         "llh_last": llh_last,
         **extras,
     }
-    if world == 1 and not args.no_cpu_baseline:
+    if world == 1 and args.full and not args.no_cpu_baseline:
         try:
             out["cpu_baseline"] = cpu_baseline(wl["codes"], wl["in_off"], W, K, wl["v0"], wl["alpha"], wl["q"], args.cpu_sample,
                                                args.cpu_iters, args.ss)
@@ -654,6 +668,19 @@ def from_seed_extras(bm, ctx, seqs, wl, args, sync):
     return out
 
 
+def dump_outputs(em, out_dir):
+    """--dump-outputs: what a caller of the timed iterate() call reads back from its handle after the last pass -- the
+    model v, the counts of the M-step that produced it, and the (llh, v_diff) trace of every pass of the handle.  The
+    workload is seeded, so the same arguments give the same inputs in every run.  At most 320 KB at the BASELINE.json
+    configurations; an array beyond DUMP_CAP_WORDS (high orders) is written as every n-th element, the same elements in
+    every run."""
+    os.makedirs(out_dir, exist_ok=True)
+    llh, v_diff, _ = em.trace()
+    for name, a in (("v", em.getV()), ("counts", em.getCounts()), ("llh", llh), ("v_diff", v_diff)):
+        a = a[:: -(-a.size // DUMP_CAP_WORDS)] if a.size > DUMP_CAP_WORDS else a
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, np.float32))
+
+
 def merge_first_call(extras, first):
     """`from_seed` carries the first-call figures beside the per-step ones."""
     if first:
@@ -697,7 +724,7 @@ def main_inprocess(args, result_fd):
             ctx.set_tuning(fused_update=0)
         b, e = packed.shard_range(W, r, N)
         ss = bm.SeqSet(ctx, packed, b, e)
-        if N == 1 and not args.force_dist and not args.no_extras:
+        if N == 1 and not args.force_dist and args.full and not args.no_extras:
             first = first_call(bm, ctx, ss, wl, args, ctx.sync)
         em = bm.EM(ctx, ss, K, W, wl["vbg"], wl["A"], wl["v0"], wl["q"], bg_order=2, max_iterations=args.steps + args.warmup + 8,
                    n_seqs_bound=args.nseq)
@@ -786,6 +813,8 @@ def main_inprocess(args, result_fd):
     agree = all(np.array_equal(v0_, em.getV()) for em in ems[1:])
     if not agree:
         raise SystemExit("bench.py: the ranks' models differ after the run")
+    if args.dump_outputs:
+        dump_outputs(ems[0], args.dump_outputs)
     kernel = [em.kernel_time() for em in ems]
     kernel_ms, launches = max(kernel)                        # the slowest rank's sequence kernel
     llh, _, _ = ems[0].trace()
@@ -810,7 +839,7 @@ def main_inprocess(args, result_fd):
         dt, kernel_ms, launches, allreduce_kind = choose_headline(args, extras, dt, kernel_ms, launches, allreduce_kind,
                                                                    hashlib.sha256(v0_.tobytes()).hexdigest()[:16])
     wd.phase("from-seed figures, CPU baseline, report", 1200)
-    if N == 1 and not comms and not args.no_extras:
+    if N == 1 and not comms and args.full and not args.no_extras:
         extras.update(from_seed_extras(bm, ctxs[0], seqs[0], wl, args, ctxs[0].sync))
     merge_first_call(extras, first)
     lp = int(seqs[0].off[-1])
@@ -884,7 +913,7 @@ def main():
     begin, end = packed.shard_range(W, rank, world)
     seqs = bm.SeqSet(ctx, packed, begin, end)
     first = None
-    if world == 1 and not use_dist and not args.no_extras:
+    if world == 1 and not use_dist and args.full and not args.no_extras:
         with torch.cuda.stream(tstream):
             first = first_call(bm, ctx, seqs, wl, args, torch.cuda.synchronize)
     em = bm.EM(ctx, seqs, K, W, vbg, A, v0, q, bg_order=2, max_iterations=args.steps + args.warmup + 8,
@@ -995,7 +1024,9 @@ def main():
     my_ar_us = None
     if use_dist and keep and isinstance(keep[0], bm.Comm):
         my_ar_us = keep[0].time_allreduce(4 ** (K + 1) * W + 3, args.allreduce_iters)      # collective, outside the timed region
-    if world == 1 and not use_dist and not args.no_extras:
+    if args.dump_outputs and rank == 0:
+        dump_outputs(em, args.dump_outputs)
+    if world == 1 and not use_dist and args.full and not args.no_extras:
         with torch.cuda.stream(tstream):
             extras = from_seed_extras(bm, ctx, seqs, wl, args, torch.cuda.synchronize)
     merge_first_call(extras, first)

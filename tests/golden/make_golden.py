@@ -265,6 +265,33 @@ def run_mask_cases(R):
         print("wrote mask", c.name)
 
 
+def run_live_cases(R):
+    """reference_live.npz: what the two tests that re-run the reference where oracle/_ref exists compare against where it
+    does not -- the first pass of small_k2_ds_N (tests/test_golden_cpu.py::test_golden_is_fresh_against_the_reference_build)
+    and EM::mask with optimizeQ on k1_heavyN at f = 0.1 (tests/test_mask_cpu.py::test_live_reference_mask_if_built)."""
+    out = {}
+    c = Case(**next(d for d in SMALL_CASES if d["name"] == "k2_ds_N"))
+    S = R.session(c.codes, c.in_off, c.ss, 42)
+    out["fresh_kmer"] = S.kmers()
+    bg, out["fresh_vbg"] = S.bg(c.bg_order, c.alpha_bg)
+    m = S.motif(c.W, c.K, c.alpha, bg, c.q, c.v0)
+    e = S.em(m, bg, False, False)
+    S.R.ref_em_estep(e); S.R.ref_em_mstep(e)
+    out["fresh_v_0"] = S.motif_v(m)
+    S.close()
+    c = Case(**SMALL_CASES[3])
+    S = R.session(c.codes, c.in_off, c.ss, 42)
+    out["mask_kmer_sha256"] = digest(S.kmers())
+    bg, out["mask_vbg"] = S.bg(c.bg_order, c.alpha_bg)
+    m = S.motif(c.W, c.K, c.alpha, bg, c.q, c.v0)
+    e = S.em(m, bg, True, False, 0.1)
+    S.R.ref_em_mask(e)
+    out["mask_v"], out["mask_r"], out["mask_q"] = S.motif_v(m), S.em_r(e), np.float32(S.R.ref_em_q(e))
+    S.close()
+    np.savez_compressed(os.path.join(HERE, "reference_live.npz"), **out)
+    print("wrote reference_live")
+
+
 def main():
     if not oracle.have_reference():
         raise SystemExit("oracle/_ref/libbammref.so missing: run `make -C oracle ref` in the dev container")
@@ -272,6 +299,9 @@ def main():
     R.set_threads(1)
     if sys.argv[1:] == ["mask"]:
         run_mask_cases(R)
+        return
+    if sys.argv[1:] == ["live"]:
+        run_live_cases(R)
         return
     if sys.argv[1:] == ["config5"]:
         run_config5_case(R)
@@ -289,6 +319,7 @@ def main():
                 print("wrote", c.name)
         return
     run_mask_cases(R)
+    run_live_cases(R)
     run_config5_case(R)
     run_eval_case(R)
     run_travis_case(R)

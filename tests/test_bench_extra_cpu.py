@@ -142,3 +142,28 @@ def test_choose_headline_takes_the_faster_region_only_when_the_in_kernel_one_is_
     assert bench.choose_headline(types.SimpleNamespace(steps=10, headline_collective="rccl"), ex, 0.0015, 1.4, 10, "k", "aa")[0] == 0.0015
     ex = dict(peer_ok, ms_per_step_peer_allreduce=0.2)
     assert bench.choose_headline(types.SimpleNamespace(steps=10, headline_collective="peer"), ex, 0.0015, 1.4, 10, "k", "aa")[0] == 0.0012
+
+
+def test_plain_run_leaves_the_full_figures_out(monkeypatch):
+    monkeypatch.setattr("sys.argv", ["bench.py", "--gpus", "1", "--steps", "9", "--warmup", "2"])
+    args = bench.parse()
+    assert args.steps == 9 and args.warmup == 2 and not args.full and args.dump_outputs is None
+    monkeypatch.setattr("sys.argv", ["bench.py", "--full", "--dump-outputs", "out"])
+    args = bench.parse()
+    assert args.full and args.dump_outputs == "out"
+
+
+def test_dump_outputs_writes_float32_and_caps_large_arrays(tmp_path, monkeypatch):
+    class EM:
+        def trace(self): return np.arange(5, dtype=np.float32), np.ones(5, np.float32), np.zeros(5, np.float32)
+        def getV(self): return np.arange(100, dtype=np.float32)
+        def getCounts(self): return np.arange(100, dtype=np.float32) * 2
+
+    bench.dump_outputs(EM(), str(tmp_path / "d"))
+    assert np.array_equal(np.load(tmp_path / "d" / "v.npy"), np.arange(100, dtype=np.float32))
+    assert np.array_equal(np.load(tmp_path / "d" / "llh.npy"), np.arange(5, dtype=np.float32))
+    assert all(np.load(tmp_path / "d" / f"{n}.npy").dtype == np.float32 for n in ("v", "counts", "llh", "v_diff"))
+    monkeypatch.setattr(bench, "DUMP_CAP_WORDS", 30)                 # beyond the cap: every n-th element, never more than the cap
+    bench.dump_outputs(EM(), str(tmp_path / "s"))
+    v = np.load(tmp_path / "s" / "v.npy")
+    assert len(v) <= 30 and np.array_equal(v, np.arange(0, 100, 4, dtype=np.float32))

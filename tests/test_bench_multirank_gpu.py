@@ -107,10 +107,32 @@ def test_two_processes_under_the_launcher_with_the_library_communicator():
 @pytest.mark.timeout(600)
 def test_first_call_figures_on_one_gpu():
     """from_seed.first_create_ms / first_call_ms: the first handle of the process, nothing warmed up."""
-    one = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--nseq", "50000", "--steps", "6", "--warmup", "2", "--no-cpu-baseline"],
+    one = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--nseq", "50000", "--steps", "6", "--warmup", "2", "--full", "--no-cpu-baseline"],
                          capture_output=True, text=True, cwd=ROOT)
     assert one.returncode == 0, one.stderr[-2000:]
     j = json.loads([l for l in one.stdout.splitlines() if l.startswith("{")][-1])
     fs = j["from_seed"]
     assert fs["first_call_passes"] == 20 and 0 < fs["first_call_ms"] < 200 and 0 < fs["first_create_ms"] < 500, fs
     assert fs["ms_per_step_iterate"] > 0 and fs["ms_per_step_optimize"] > 0
+
+
+@pytest.mark.timeout(600)
+def test_plain_run_times_the_steps_alone_and_dumps_what_they_computed(tmp_path):
+    """A plain run prints the headline without the --full figures; --dump-outputs writes the timed handle's model, counts
+    and trace, the same bytes in a second run with the same arguments (seeded inputs, integer accumulation)."""
+    import numpy as np
+    lines = []
+    for d in ("a", "b"):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--nseq", "20000", "--steps", "7", "--warmup", "3",
+                            "--dump-outputs", str(tmp_path / d)], capture_output=True, text=True, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines.append(json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1]))
+    j = lines[0]
+    assert j["steps"] == 7 and j["warmup"] == 3 and j["ms_per_step"] > 0 and j["value"] > 0
+    assert "cpu_baseline" not in j and "from_seed" not in j
+    for name in ("v", "counts", "llh", "v_diff"):
+        a, b = np.load(tmp_path / "a" / f"{name}.npy"), np.load(tmp_path / "b" / f"{name}.npy")
+        assert a.dtype == np.float32 and np.array_equal(a, b), name
+    llh = np.load(tmp_path / "a" / "llh.npy")
+    assert len(llh) == 3 + 7 and llh[-1] == np.float32(j["llh_last"])          # every pass of the handle, the timed ones last
+    assert np.load(tmp_path / "a" / "v.npy").shape == (20 * (4 ** 4 - 4) // 3,)  # W = 20, k = 2
