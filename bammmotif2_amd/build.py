@@ -15,7 +15,8 @@ import subprocess
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libbamm_em.so")
-SOURCES = ["model.hip", "kernels.hip", "grouped.hip", "grouped_long.hip", "grouped_xl.hip", "grouped_mix.hip", "grouped_mix1.hip", "mask.hip", "seed.hip", "long_seq.hip", "prep.hip", "negs.hip", "abi.cpp", "comm.cpp", "pack.cpp"]
+SOURCES = ["model.hip", "kernels.hip", "grouped.hip", "grouped_long.hip", "grouped_xl.hip", "grouped_mix.hip", "grouped_mix1.hip", "mask.hip", "seed.hip", "long_seq.hip", "prep.hip", "negs.hip", "ctx.cpp", "seqs.cpp", "plan.cpp", "em_pass.cpp", "em.cpp",
+           "score.cpp", "comm.cpp", "pack.cpp"]
 HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "device_utils.h"), os.path.join(CSRC, "grouped_kernel.h"), os.path.join(CSRC, "mixed_kernel.h"), os.path.join(CSRC, "update_kernel.h"), os.path.join(CSRC, "phase_clock.h"),
            os.path.join(HERE, "..", "include", "bamm_em.h")]
 # -Rpass-analysis=kernel-resource-usage: registers / scratch / spills of every kernel go to the compiler's
@@ -115,9 +116,12 @@ def _stale(target: str, deps) -> bool:
     return any(os.path.getmtime(d) > t for d in deps if os.path.exists(d))
 
 
-# headers only some translation units include (a change there does not rebuild the sequence kernels)
+# headers only some translation units include (a change there does not rebuild the sequence kernels); handles.h, which
+# includes prep.h, is the private header of the C ABI's host units
+_HANDLES = [os.path.join(CSRC, "handles.h"), os.path.join(CSRC, "prep.h")]
 EXTRA_DEPS = {"prep.hip": [os.path.join(CSRC, "prep.h")], "negs.hip": [os.path.join(CSRC, "negs.h")],
-              "abi.cpp": [os.path.join(CSRC, "prep.h"), os.path.join(CSRC, "negs.h"), os.path.join(CSRC, "glibc_rand.h")],
+              "ctx.cpp": _HANDLES, "plan.cpp": _HANDLES, "em_pass.cpp": _HANDLES, "em.cpp": _HANDLES, "score.cpp": _HANDLES,
+              "seqs.cpp": _HANDLES + [os.path.join(CSRC, "negs.h"), os.path.join(CSRC, "glibc_rand.h")],
               "pack.cpp": [os.path.join(CSRC, "glibc_rand.h"), os.path.join(CSRC, "prep.h")]}
 FLAGS_STAMP = os.path.join(OBJDIR, "flags.txt")
 

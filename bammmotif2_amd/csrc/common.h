@@ -55,7 +55,7 @@ inline size_t v_size(size_t K, size_t W) { return v_offset(K + 1, W); }
 inline size_t bg_offset(size_t k) { return (ipow4(k + 1) - 4) / 3; }
 inline size_t bg_size(size_t K) { return bg_offset(K + 1); }
 
-// internals shared between abi.cpp and comm.cpp
+// internals shared between the C ABI's host units (handles.h) and comm.cpp
 int ctx_device(const bamm_ctx* c);
 hipStream_t ctx_stream(const bamm_ctx* c);
 int comm_allreduce_i64(bamm_comm* c, void* dev_ptr, size_t n_words, hipStream_t st);   // ncclAllReduce(ncclInt64, ncclSum)

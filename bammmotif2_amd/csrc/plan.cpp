@@ -1,0 +1,284 @@
+// The launch plan of an EM handle (bamm_em_create): the column slices of tables beyond the fused kernel's LDS, the
+// split of every length bucket into grouped-column and per-column launches, the blocks of each launch, the launch that
+// carries the fused update and the sliced path's lists.  Host code only.
+
+#include <atomic>
+#include <cmath>
+
+#include "handles.h"
+
+namespace bamm {
+
+namespace {
+
+constexpr size_t kLds = 160 * 1024;
+
+// Make the kernel(s) one bucket's passes launch ready ahead of the first pass: the HIP runtime loads a translation unit's
+// code object on the first use of any kernel in it (0.8 ms for the mixed-row kernels, 8-14 ms for the 4 MB units), which
+// otherwise lands in the handle's first pass.  Runs on a thread of its own beside bamm_em_create's host work.
+int prime_bucket(bamm_ctx* c, const bamm_em_params& prm, uint32_t Y, bool sliced, const EmBucket& eb) {
+    if (hipSetDevice(c->device) != hipSuccess) { set_error("hipSetDevice failed"); return BAMM_ERR_HIP; }
+    EmKernelArgs a{};
+    a.K = prm.K; a.W = prm.W; a.Y = Y;
+    if (eb.mclass == kLongClass) return launch_long_em(a, true, false, false, kPrimeOnly, c->stream);
+    const uint32_t threads = bucket_threads(c, eb);
+    if (sliced || !eb.grouped) {                             // k_em_seq, the slices and the list walk share kernels.hip
+        a.logC = 0;
+        return launch_em_seq(eb.mclass, false, false, a, kPrimeOnly, threads, c->stream);
+    }
+    GrpKernelArgs ga{};
+    ga.e = a;
+    if (!grp_geometry(prm.K, prm.W, eb.G, kMClasses[eb.mclass], threads / 64u, true, eb.logc, eb.layout, &ga.g)) return BAMM_OK;   // (the launch reports it)
+    return launch_em_grp(eb.mclass, true, false, ga, kPrimeOnly, threads, c->stream);
+}
+
+}  // namespace
+
+uint32_t default_threads(const bamm_ctx* c, int mclass) {
+    uint32_t t = c->threads ? c->threads : max_threads_for_mclass(mclass);
+    return std::min(t, max_threads_for_mclass(mclass));
+}
+
+// block size of one launch: the grouped kernel's longer length classes are built for fewer waves
+uint32_t bucket_threads(const bamm_ctx* c, const EmBucket& b) {
+    if (b.mclass == kLongClass) return 256u;
+    const uint32_t t = default_threads(c, b.mclass);
+    return b.grouped ? std::min(t, grp_max_threads(kMClasses[b.mclass])) : t;
+}
+
+uint32_t default_blocks(const bamm_ctx* c, uint32_t threads) {
+    if (c->blocks) return c->blocks;
+    const uint32_t cus = c->num_cus > 0 ? (uint32_t)c->num_cus : 256u;
+    return cus * std::max(1u, 2048u / threads);       // fill 32 waves per CU
+}
+
+bool plan_slices(bamm_em* em) {
+    const bamm_em_params* prm = &em->prm;
+    const bamm_ctx* c = em->ctx;
+    const uint32_t Y = em->Y;
+    bool sliced = em_lds_bytes(prm->W, Y, true, 0, 0) > kLds;
+    uint32_t e_cols = 0, m_cols = 0;
+    // orders 7..10 (kmer_ spans 11 bases, Sequence.cpp:37): not even one column of the odds / count tables (4^(K+1) rows)
+    // fits the 160 KiB of a CU.  Those models run with their tables in global memory (long_seq.hip: every window
+    // multiplies its W odds straight from the table, the fixed-point addends go straight into the pass's
+    // accumulator) -- the same integers, written for coverage, not speed.
+    bool global_tables = false;
+    if (sliced) {
+        while (e_cols < prm->W && e_slice_lds_bytes(e_cols + 1, Y) <= kLds) e_cols++;
+        while (m_cols < prm->W && m_slice_lds_bytes(m_cols + 1, Y, 0) <= kLds) m_cols++;
+        if (e_cols == 0 || m_cols == 0) { global_tables = true; sliced = false; }
+    }
+    em->sliced = sliced;
+    if (sliced) {
+        auto cut = [&](uint32_t max_cols, std::vector<std::pair<uint32_t, uint32_t>>& out) {
+            const uint32_t n = (prm->W + max_cols - 1) / max_cols, per = (prm->W + n - 1) / n;
+            for (uint32_t j = 0; j < prm->W; j += per) out.emplace_back(j, std::min(prm->W, j + per));
+            return per;
+        };
+        cut(e_cols, em->e_slices);
+        em->e_fused = em_lds_bytes(prm->W, Y, false, 0, 0) <= kLds && c->use_e_fused;
+        // sparse M-slices: room for a list of 256 windows + the y of every position per wave (8 waves per
+        // block at the longest length class) is taken off the column budget when that costs no extra slice
+        int mc_max = 0;                                      // longest length class present (the long bucket has no class)
+        for (auto& b : em->seqs->buckets) mc_max = std::max(mc_max, b.mclass);
+        const int Mmax = kMClasses[mc_max];
+        const uint32_t waves = max_threads_for_mclass(mc_max) / 64u;
+        const size_t scratch = !c->use_sparse ? 0 : m_slice_wave_bytes(Mmax, 256) * waves;
+        uint32_t m_cols_sparse = 0;
+        while (scratch && m_cols_sparse < prm->W && m_slice_lds_bytes(m_cols_sparse + 1, Y, 0) + scratch <= kLds) m_cols_sparse++;
+        // ... and when it would, the widest slices stay and every bucket takes the longest list that still
+        // fits beside them (run_accumulate): at k=4, W=30 a 128-entry list next to the 120 KB count slice
+        // is worth 20 % of the iteration
+        const bool roomy = m_cols_sparse && (prm->W + m_cols_sparse - 1) / m_cols_sparse == (prm->W + m_cols - 1) / m_cols;
+        if (roomy) m_cols = m_cols_sparse;
+        if (scratch) em->m_slice_cap = 256;
+        const uint32_t per_m = cut(m_cols, em->m_slices);
+        const size_t used = roomy ? scratch : std::min(scratch, kLds - std::min(kLds, m_slice_lds_bytes(per_m, Y, 0)));
+        while (em->m_slice_logc < 4 && m_slice_lds_bytes(per_m, Y, em->m_slice_logc + 1) + used <= kLds) em->m_slice_logc++;
+    }
+    return global_tables;
+}
+
+int plan_launches(bamm_em* em, bool global_tables, const uint8_t* seq_mask, Primers& primers) {
+    const bamm_em_params* prm = &em->prm;
+    bamm_ctx* c = em->ctx;
+    bamm_seqs* seqs = em->seqs;
+    const uint32_t Y = em->Y;
+    const bool sliced = em->sliced;
+    hipStream_t st = c->stream;
+    int rc = BAMM_OK;
+    // the code objects of the kernels the handle will launch are loaded beside the host work below (prime_bucket), each as
+    // soon as the plan names the kernel
+    auto prime = [&primers, c, prm_copy = em->prm, Y, sliced](const EmBucket& eb) {
+        primers.t.emplace_back([c, prm_copy, Y, sliced, eb] { (void)prime_bucket(c, prm_copy, Y, sliced, eb); });
+    };
+    // launches of one pass: every length bucket, split into the sequences the grouped-column kernel
+    // takes (no exception, or all of them within its virtual rows) and the rest
+    const bool want_grouped = !sliced && prm->K <= 3u && c->use_grouped;
+    // A shard of a sharded set plans its kernels as the whole set would: which rows a sequence is multiplied through
+    // (mixed or uniform) decides the last bit of its responsibilities, so the choice follows the GLOBAL size the caller
+    // names (n_seqs_bound / n_seqs_global; this shard's own count when it names neither) and nothing about the shard:
+    // every length class of a set of `plan_n` sequences is planned as a launch of that many (a class that holds a small
+    // part of a large set pays the larger tables' few microseconds per launch; an estimate of the class's global share
+    // from this shard's own mix of lengths could differ between ranks next to the threshold).  The other input of the
+    // plan, whether most sequences of a class carry exceptions, is the shard's own: a property of the data that holds
+    // for every shard alike on double-stranded sets (each sequence has its strand junction) and on clean single-stranded ones.
+    const uint64_t plan_n = std::max<uint64_t>(std::max<uint64_t>(prm->n_seqs_bound, prm->n_seqs_global), seqs->n);
+    for (auto& b : seqs->buckets) {
+        if (b.mclass == kLongClass || global_tables) {       // beyond the length classes / tables beyond LDS: long_seq.hip
+            EmBucket eb;
+            eb.mclass = kLongClass; eb.count = b.count; eb.d_idx = b.d_idx;
+            eb.work = b.mclass == kLongClass ? b.work : (double)b.count * kMClasses[b.mclass];
+            em->ebuckets.push_back(eb);
+            prime(eb);
+            continue;
+        }
+        const int Mcls = kMClasses[b.mclass];
+        const uint32_t threads = default_threads(c, b.mclass);
+        GrpGeom gg{};
+        uint32_t glogc = 0, gG = 0;
+        const ExcK::XRec* xr = nullptr;
+        std::vector<uint32_t> yes, no;
+        uint32_t glayout = 0;
+        // do most sequences of this bucket carry exceptions (a double-stranded set: all of them)?
+        std::atomic<size_t> with_exc_a{0};
+        host_ranges(b.count, [&](uint64_t i0, uint64_t i1) {
+            size_t cnt = 0;
+            for (uint64_t i = i0; i < i1; i++) {
+                const uint32_t n = b.d_idx ? b.h_idx[i] : (uint32_t)i;
+                cnt += em->exc->h_off[n + 1] != em->exc->h_off[n];
+            }
+            with_exc_a.fetch_add(cnt, std::memory_order_relaxed);
+        });
+        const size_t with_exc = with_exc_a.load();
+        if (want_grouped && grp_supported_class(Mcls, prm->K) &&
+            grp_plan(prm->K, prm->W, Mcls, std::min(threads, grp_max_threads(Mcls)) / 64u, 2 * with_exc > b.count, plan_n * (uint64_t)Mcls >= 40000ull * 7ull, c->group_size, c->group_layout, &gG, &glogc, &glayout) &&
+            grp_geometry(prm->K, prm->W, gG, Mcls, std::min(threads, grp_max_threads(Mcls)) / 64u, true, glogc, glayout, &gg)) {
+            { EmBucket pb; pb.mclass = b.mclass; pb.grouped = true; pb.logc = glogc; pb.G = gG; pb.layout = glayout; prime(pb); }
+            if ((rc = xrec_for_group(seqs, prm->K, gG, em->exc, &xr))) return rc;
+            // exceptions within the virtual rows for them, and clear of the rows for the LW1 edge
+            auto capable = [&](uint32_t n) {
+                const uint32_t B = xr->h_B[n];
+                return B == 0u || (B <= gg.Bj && (gg.np != 0u || xr->h_lo[n] + B + gg.G <= seqs->h_len[n] - prm->W + 1u));
+            };
+            std::atomic<bool> all_capable{true};
+            host_ranges(b.count, [&](uint64_t i0, uint64_t i1) {
+                for (uint64_t i = i0; i < i1 && all_capable.load(std::memory_order_relaxed); i++)
+                    if (!capable(b.d_idx ? b.h_idx[i] : (uint32_t)i)) all_capable.store(false, std::memory_order_relaxed);
+            });
+            const bool all = all_capable.load();
+            if (!all)
+                for (uint32_t i = 0; i < b.count; i++) {
+                    const uint32_t n = b.d_idx ? b.h_idx[i] : i;
+                    (capable(n) ? yes : no).push_back(n);
+                }
+            EmBucket eb;
+            eb.mclass = b.mclass; eb.grouped = true; eb.logc = glogc; eb.G = gG; eb.layout = glayout; eb.d_xrec = xr->d_xrec;
+            if (all) { eb.count = b.count; eb.d_idx = b.d_idx; }
+            else {
+                uint32_t* d = nullptr;
+                if ((rc = dev_upload(c, &d, yes.data(), yes.size()))) return rc;
+                em->owned_idx.push_back(d);
+                eb.count = (uint32_t)yes.size(); eb.d_idx = d;
+            }
+            eb.work = (double)eb.count * Mcls * 0.6;       // grouped passes cost about 60 % per sequence
+            if (eb.count) em->ebuckets.push_back(eb);
+            if (all) continue;
+        }
+        EmBucket eb;
+        eb.mclass = b.mclass;
+        if (!no.empty()) {
+            uint32_t* d = nullptr;
+            if ((rc = dev_upload(c, &d, no.data(), no.size()))) return rc;
+            em->owned_idx.push_back(d);
+            eb.count = (uint32_t)no.size(); eb.d_idx = d;
+        } else { eb.count = b.count; eb.d_idx = b.d_idx; }
+        eb.work = (double)eb.count * Mcls;
+        em->ebuckets.push_back(eb);
+        prime(eb);
+    }
+    if (!em->owned_idx.empty() && hipStreamSynchronize(st) != hipSuccess) { set_error("stream sync failed"); return BAMM_ERR_HIP; }
+    // launch geometry: blocks split over the launches in proportion to their work
+    double total_work = 0;
+    for (auto& b : em->ebuckets) total_work += b.work;
+    em->total_blocks = 0;
+    for (auto& b : em->ebuckets) {
+        if (b.mclass == kLongClass) {                        // a workgroup per sequence
+            b.blocks = std::min(b.count, (uint32_t)std::max(1, c->num_cus) * 8u);
+            em->total_blocks += b.blocks;
+            continue;
+        }
+        const uint32_t threads = bucket_threads(c, b);
+        // 16 waves per CU saturate the LDS pipe (tools/lds_bench2.hip); the LDS left over goes
+        // into private copies of the count table
+        const uint32_t blocks_per_cu = sliced ? 1u : std::max(1u, 1024u / threads);
+        if (!b.grouped) {
+            // sparse M-step scratch (per wave) competes with the private copies for LDS; it is only
+            // enabled when at least 4 copies survive next to it
+            const int Mcls = kMClasses[b.mclass];
+            size_t scratch = sliced ? 0 : sparse_wave_bytes(Mcls) * (threads / 64u);
+            uint32_t cap = sliced ? 0u : sparse_cap_for(Mcls);
+            if (!c->use_sparse) { cap = 0; scratch = 0; }
+            if (cap && (em_lds_bytes(prm->W, Y, true, 0, scratch) > kLds / blocks_per_cu ||
+                        pick_log_copies(prm->W, Y, blocks_per_cu, scratch) + 1 < pick_log_copies(prm->W, Y, blocks_per_cu, 0))) {
+                cap = 0;
+                scratch = 0;
+            }
+            b.sparse_cap = cap;
+            b.sparse_bytes = (uint32_t)(cap ? sparse_wave_bytes(Mcls) : 0);
+            b.logc = sliced ? 0u : pick_log_copies(prm->W, Y, blocks_per_cu, scratch);
+        }
+        const uint32_t per_cu = b.grouped ? 1u : blocks_per_cu;
+        const uint32_t all = c->blocks ? c->blocks : (uint32_t)std::max(1, c->num_cus) * per_cu;
+        uint32_t nb = (uint32_t)std::max(1.0, std::floor(all * (b.work / total_work) + 0.5));
+        const uint32_t waves_per_block = threads / 64u;
+        nb = std::min(nb, (b.count + waves_per_block - 1) / waves_per_block);
+        nb = std::max(nb, 1u);
+        b.blocks = nb;
+        em->total_blocks += nb;
+    }
+    // fused updates (update_kernel.h): inside iterate() / optimize() the model update of pass p runs in the block
+    // prologue of pass p+1's FIRST launch -- a grouped kernel whose count tables leave room for the update's scratch
+    if (!sliced && c->use_fused_update && update_fits_lds(prm->K, prm->W) && prm->K <= 2u) {
+        size_t best = em->ebuckets.size();
+        for (size_t i = 0; i < em->ebuckets.size(); i++)
+            if (em->ebuckets[i].grouped && kMClasses[em->ebuckets[i].mclass] <= BAMM_FUSE_MAX_M &&   // the classes built with the fused prologue
+                (best == em->ebuckets.size() || em->ebuckets[i].count > em->ebuckets[best].count)) best = i;
+        if (best < em->ebuckets.size()) {
+            std::swap(em->ebuckets[0], em->ebuckets[best]);
+            const EmBucket& eb = em->ebuckets[0];
+            GrpGeom g{};
+            const uint32_t threads = bucket_threads(c, eb);
+            if (grp_geometry(prm->K, prm->W, eb.G, kMClasses[eb.mclass], threads / 64u, true, eb.logc, eb.layout, &g)) {
+                const uint32_t need = (uint32_t)update_lds_bytes(prm->K, prm->W);
+                const uint32_t s1_bytes = (prm->W * (Y + 1u) * 4u + 15u) & ~15u;
+                // mixed rows: behind the staged single-column table, inside the count tables; uniform rows: the count table
+                const uint32_t off = (eb.layout & 8u) ? g.off_s1 + s1_bytes : g.off_ng;
+                const uint32_t end = (eb.layout & 8u) ? g.off_wave : g.off_n1;
+                if (off + need <= end) {
+                    em->fusable = true;
+                    em->fuse_upd_off = off;
+                    if ((rc = dev_alloc(&em->d_s_block, (size_t)eb.blocks * prm->W * (Y + 1u)))) return rc;
+                }
+            }
+        }
+    }
+    if (sliced && em->e_fused && c->use_e_list) {
+        if ((rc = scratch_alloc(c, &em->d_list_r, (size_t)seqs->total_len)) || (rc = scratch_alloc(c, &em->d_list_p, (size_t)seqs->total_len)) ||
+            (rc = dev_alloc(&em->d_list_n, (size_t)seqs->n))) return rc;
+        if (hipMemsetAsync(em->d_list_n, 0, (seqs->n ? seqs->n : 1) * sizeof(uint32_t), st) != hipSuccess) { set_error("hipMemsetAsync failed"); return BAMM_ERR_HIP; }
+        // lists or dense r, per pass: the first pass of a handle takes the dense flavour (nothing is known yet: the
+        // counter starts saturated), later ones lists once fewer than list_threshold_pct of the windows are non-zero
+        if ((rc = dev_alloc(&em->d_nnz, 2))) return rc;
+        const unsigned long long start[2] = {~0ull, 0ull};
+        if (hipMemcpyAsync(em->d_nnz, start, sizeof start, hipMemcpyHostToDevice, st) != hipSuccess) { set_error("hipMemcpyAsync failed"); return BAMM_ERR_HIP; }
+        unsigned long long windows = 0;
+        for (uint64_t n = 0; n < seqs->n; n++) windows += seqs->h_len[n] - prm->W + 1u;
+        if (seq_mask && seqs->n) windows = (unsigned long long)((double)windows * (double)em->n_active / (double)seqs->n);
+        em->nnz_limit = windows / 100u * c->list_threshold_pct;
+        em->adaptive_lists = c->use_adaptive_lists;
+    }
+    return BAMM_OK;
+}
+
+}  // namespace bamm

@@ -190,6 +190,11 @@ def test_without_the_tuning_or_on_an_unfit_handle_the_collective_stays(gpu_ctx, 
     out, errs = _local_ranks(2, c4, orc, lambda em, r: (em.comm_mode(), em.iterate(2), em.getV())[::2])
     assert errs == [None, None] and out[0][0][0] == 1 and "not one launch of a grouped-column kernel built with the tail" in out[0][0][1]
     assert np.array_equal(out[0][1], out[1][1])
+    c1 = Case("one_seq", N=1, L0=200, W=20, K=2, seed=33)    # rank 1's shard is empty: its handle plans no launch at all
+    out, errs = _local_ranks(2, c1, orc, lambda em, r: (em.comm_mode(), em.iterate(2), em.getV())[::2])
+    assert errs == [None, None] and out[0][0][0] == 1 and out[1][0][0] == 1
+    assert "not one launch of a grouped-column kernel built with the tail" in out[1][0][1]
+    assert np.array_equal(out[0][1], out[1][1])
 
 
 @pytest.mark.parametrize("shape", ["mix_k2_ds", "grp_k1_ds"])

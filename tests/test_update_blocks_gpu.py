@@ -59,7 +59,7 @@ def test_update_over_blocks_equals_one_block(shape, gpu_ctx):
 
 
 def test_scratch_blocks_pass_from_handle_to_handle(gpu_ctx):
-    """The context keeps a closed handle's set-sized scratch for the next one (csrc/abi.cpp: scratch_alloc): same
+    """The context keeps a closed handle's set-sized scratch for the next one (csrc/ctx.cpp: scratch_alloc_bytes): same
     results from a block that is fresh, reused, reused after a LARGER owner, and with the cache turned off."""
     shape = dict(N=6000, L0=400, W=24, K=4, n_frac=0.01, ragged=60)      # sliced path: dense r, lists
     small = dict(N=3000, L0=300, W=24, K=4)
