@@ -49,6 +49,16 @@ inline int prime_kernel(const void* kernel) {
     return BAMM_OK;
 }
 
+// one kernel launch: allow_lds, then the launch -- or, when blocks == kPrimeOnly, prime_kernel instead (the caller
+// checks hipGetLastError)
+template <class... P, class... A>
+int launch_kernel(void (*k)(P...), uint32_t blocks, uint32_t threads, size_t lds, hipStream_t st, A... args) {
+    if (int rc = allow_lds(reinterpret_cast<const void*>(k), lds)) return rc;
+    if (blocks == kPrimeOnly) return prime_kernel(reinterpret_cast<const void*>(k));
+    hipLaunchKernelGGL(k, dim3(blocks), dim3(threads), lds, st, args...);
+    return BAMM_OK;
+}
+
 inline size_t ipow4(size_t e) { return size_t(1) << (2 * e); }
 inline size_t v_offset(size_t k, size_t W) { return W * ((ipow4(k + 1) - 4) / 3); }
 inline size_t v_size(size_t K, size_t W) { return v_offset(K + 1, W); }

@@ -7,6 +7,9 @@
 namespace bamm {
 namespace {
 
+// v_offset (common.h) for device code: the flat [k][y][j] tables' first cell of order k, in 32-bit order arithmetic
+__device__ __forceinline__ size_t v_off(uint32_t k, uint32_t W) { return (size_t)W * (((size_t(1) << (2 * (k + 1))) - 4) / 3); }
+
 // ---- cross-lane helpers ------------------------------------------------------------------
 // DPP wave shifts exist on the GFX9 family (incl. gfx950).  `oldv` is what lane 0 keeps.
 __device__ __forceinline__ float wave_shr1(float oldv, float x) {

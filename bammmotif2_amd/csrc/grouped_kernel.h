@@ -831,29 +831,15 @@ int launch_variant(bool accum, bool write_r, const GrpKernelArgs& a, uint32_t bl
         return BAMM_ERR_UNSUPPORTED;
     } else {
         const size_t lds = a.g.lds_bytes;
-        int rc;
-        if (write_r) {
-            if ((rc = allow_lds(reinterpret_cast<const void*>(&k_em_grp<M, G, KG, false, true, THREADS>), lds))) return rc;
-            if (blocks == kPrimeOnly) return prime_kernel(reinterpret_cast<const void*>(&k_em_grp<M, G, KG, false, true, THREADS>));
-            hipLaunchKernelGGL((k_em_grp<M, G, KG, false, true, THREADS>), dim3(blocks), dim3(threads), lds, st, a);
-        } else if (accum) {
-            if constexpr (KG - G != 3 && M <= BAMM_FUSE_MAX_M) {             // the classes built with the all-reduce tail
-                if (a.peer.world > 1u) {
-                    if ((rc = allow_lds(reinterpret_cast<const void*>(&k_em_grp<M, G, KG, true, false, THREADS, true>), lds))) return rc;
-                    hipLaunchKernelGGL((k_em_grp<M, G, KG, true, false, THREADS, true>), dim3(blocks), dim3(threads), lds, st, a);
-                    return BAMM_OK;
-                }
+        if (write_r) return launch_kernel(&k_em_grp<M, G, KG, false, true, THREADS>, blocks, threads, lds, st, a);
+        if (accum) {
+            if constexpr (KG - G != 3 && M <= BAMM_FUSE_MAX_M) {         // the classes built with the all-reduce tail
+                if (a.peer.world > 1u) return launch_kernel(&k_em_grp<M, G, KG, true, false, THREADS, true>, blocks, threads, lds, st, a);
             }
             if (a.peer.world > 1u) { set_error("grouped kernel: this class is not built with the in-kernel all-reduce"); return BAMM_ERR_UNSUPPORTED; }
-            if ((rc = allow_lds(reinterpret_cast<const void*>(&k_em_grp<M, G, KG, true, false, THREADS>), lds))) return rc;
-            if (blocks == kPrimeOnly) return prime_kernel(reinterpret_cast<const void*>(&k_em_grp<M, G, KG, true, false, THREADS>));
-            hipLaunchKernelGGL((k_em_grp<M, G, KG, true, false, THREADS>), dim3(blocks), dim3(threads), lds, st, a);
-        } else {
-            if ((rc = allow_lds(reinterpret_cast<const void*>(&k_em_grp<M, G, KG, false, false, THREADS>), lds))) return rc;
-            if (blocks == kPrimeOnly) return prime_kernel(reinterpret_cast<const void*>(&k_em_grp<M, G, KG, false, false, THREADS>));
-            hipLaunchKernelGGL((k_em_grp<M, G, KG, false, false, THREADS>), dim3(blocks), dim3(threads), lds, st, a);
+            return launch_kernel(&k_em_grp<M, G, KG, true, false, THREADS>, blocks, threads, lds, st, a);
         }
-        return BAMM_OK;
+        return launch_kernel(&k_em_grp<M, G, KG, false, false, THREADS>, blocks, threads, lds, st, a);
     }
 }
 

@@ -26,6 +26,7 @@
 
 #include <algorithm>
 #include <cfloat>
+#include <type_traits>
 
 namespace bamm {
 
@@ -766,21 +767,9 @@ __global__ void __launch_bounds__(THREADS) k_score(ScoreKernelArgs a) {
 template <int M, int THREADS>
 int launch_em_variant(bool accum, bool write_r, const EmKernelArgs& a, uint32_t blocks, uint32_t threads,
                       size_t lds, hipStream_t st) {
-    int rc;
-    if (write_r) {
-        if ((rc = allow_lds(reinterpret_cast<const void*>(&k_em_seq<M, false, true, THREADS>), lds))) return rc;
-        if (blocks == kPrimeOnly) return prime_kernel(reinterpret_cast<const void*>(&k_em_seq<M, false, true, THREADS>));
-        hipLaunchKernelGGL((k_em_seq<M, false, true, THREADS>), dim3(blocks), dim3(threads), lds, st, a);
-    } else if (accum) {
-        if ((rc = allow_lds(reinterpret_cast<const void*>(&k_em_seq<M, true, false, THREADS>), lds))) return rc;
-        if (blocks == kPrimeOnly) return prime_kernel(reinterpret_cast<const void*>(&k_em_seq<M, true, false, THREADS>));
-        hipLaunchKernelGGL((k_em_seq<M, true, false, THREADS>), dim3(blocks), dim3(threads), lds, st, a);
-    } else {
-        if ((rc = allow_lds(reinterpret_cast<const void*>(&k_em_seq<M, false, false, THREADS>), lds))) return rc;
-        if (blocks == kPrimeOnly) return prime_kernel(reinterpret_cast<const void*>(&k_em_seq<M, false, false, THREADS>));
-        hipLaunchKernelGGL((k_em_seq<M, false, false, THREADS>), dim3(blocks), dim3(threads), lds, st, a);
-    }
-    return BAMM_OK;
+    if (write_r) return launch_kernel(&k_em_seq<M, false, true, THREADS>, blocks, threads, lds, st, a);
+    if (accum) return launch_kernel(&k_em_seq<M, true, false, THREADS>, blocks, threads, lds, st, a);
+    return launch_kernel(&k_em_seq<M, false, false, THREADS>, blocks, threads, lds, st, a);
 }
 
 }  // namespace
@@ -812,6 +801,19 @@ uint32_t pick_log_copies(uint32_t W, uint32_t Y, uint32_t blocks_per_cu, size_t 
     X(13, 24, 512) X(14, 28, 512) X(15, 32, 512) X(16, 40, 512) X(17, 48, 512) X(18, 56, 512) X(19, 64, 512) \
     X(20, 80, 256) X(21, 96, 256) X(22, 128, 256)
 
+namespace {
+// f(M, THREADS) with the class's values as std::integral_constant arguments
+template <class F>
+int with_mclass(int mclass, F&& f) {
+    switch (mclass) {
+#define X(idx, M, T) case idx: return f(std::integral_constant<int, M>(), std::integral_constant<int, T>());
+        BAMM_FOR_EACH_MCLASS(X)
+#undef X
+        default: set_error("no kernel for M class %d", mclass); return BAMM_ERR_UNSUPPORTED;
+    }
+}
+}  // namespace
+
 int launch_em_seq(int mclass, bool accum, bool write_r, const EmKernelArgs& a, uint32_t blocks,
                   uint32_t threads, hipStream_t st) {
     const size_t lds = em_lds_bytes(a.W, a.Y, accum, a.logC, (size_t)a.sparse_wave_bytes * (threads / 64u));
@@ -824,17 +826,8 @@ int launch_em_seq(int mclass, bool accum, bool write_r, const EmKernelArgs& a, u
         set_error("bad launch geometry %u x %u for M class %d", blocks, threads, mclass);
         return BAMM_ERR_ARG;
     }
-    switch (mclass) {
-#define X(idx, M, T)                                                   \
-    case idx:                                                          \
-        if (int rc = launch_em_variant<M, T>(accum, write_r, a, blocks, threads, lds, st)) return rc; \
-        break;
-        BAMM_FOR_EACH_MCLASS(X)
-#undef X
-        default:
-            set_error("no kernel for M class %d", mclass);
-            return BAMM_ERR_UNSUPPORTED;
-    }
+    if (int rc = with_mclass(mclass, [&](auto M, auto T) { return launch_em_variant<M, T>(accum, write_r, a, blocks, threads, lds, st); }))
+        return rc;
     BAMM_HIP(hipGetLastError());
     return BAMM_OK;
 }
@@ -851,16 +844,8 @@ int launch_e_slice(int mclass, const EmKernelArgs& a, uint32_t j0, uint32_t j1, 
                    uint32_t threads, hipStream_t st) {
     const size_t lds = e_slice_lds_bytes(j1 - j0, a.Y);
     if (lds > 160 * 1024 || j1 <= j0) { set_error("bad E slice [%u,%u)", j0, j1); return BAMM_ERR_UNSUPPORTED; }
-    switch (mclass) {
-#define X(idx, M, T)                                                                                   \
-    case idx:                                                                                          \
-        if (int rc = allow_lds(reinterpret_cast<const void*>(&k_e_slice<M, T>), lds)) return rc;                 \
-        hipLaunchKernelGGL((k_e_slice<M, T>), dim3(blocks), dim3(threads), lds, st, a, j0, j1, last ? 1 : 0); \
-        break;
-        BAMM_FOR_EACH_MCLASS(X)
-#undef X
-        default: set_error("no kernel for M class %d", mclass); return BAMM_ERR_UNSUPPORTED;
-    }
+    if (int rc = with_mclass(mclass, [&](auto M, auto T) { return launch_kernel(&k_e_slice<M, T>, blocks, threads, lds, st, a, j0, j1, last ? 1 : 0); }))
+        return rc;
     BAMM_HIP(hipGetLastError());
     return BAMM_OK;
 }
@@ -869,16 +854,8 @@ int launch_m_slice(int mclass, const EmKernelArgs& a, uint32_t j0, uint32_t j1, 
                    uint32_t threads, hipStream_t st) {
     const size_t lds = m_slice_lds_bytes(j1 - j0, a.Y, a.logC) + (size_t)a.sparse_wave_bytes * (threads / 64u);
     if (lds > 160 * 1024 || j1 <= j0) { set_error("bad M slice [%u,%u)", j0, j1); return BAMM_ERR_UNSUPPORTED; }
-    switch (mclass) {
-#define X(idx, M, T)                                                                                   \
-    case idx:                                                                                          \
-        if (int rc = allow_lds(reinterpret_cast<const void*>(&k_m_slice<M, T>), lds)) return rc;                 \
-        hipLaunchKernelGGL((k_m_slice<M, T>), dim3(blocks), dim3(threads), lds, st, a, j0, j1, r_reversed ? 1 : 0); \
-        break;
-        BAMM_FOR_EACH_MCLASS(X)
-#undef X
-        default: set_error("no kernel for M class %d", mclass); return BAMM_ERR_UNSUPPORTED;
-    }
+    if (int rc = with_mclass(mclass, [&](auto M, auto T) { return launch_kernel(&k_m_slice<M, T>, blocks, threads, lds, st, a, j0, j1, r_reversed ? 1 : 0); }))
+        return rc;
     BAMM_HIP(hipGetLastError());
     return BAMM_OK;
 }
@@ -892,23 +869,14 @@ int launch_m_list(int mclass, const EmKernelArgs& a, uint32_t j0, uint32_t j1, u
     // for -- 16 waves per block where their copies of the decoded sequence still fit beside the count slice
     if (kMClasses[mclass] == 16 && threads == 768u && j1 > j0 && m_list_lds_bytes(j1 - j0, a.Y, a.logC, 16, 16u) <= 160 * 1024) {
         const size_t lds16 = m_list_lds_bytes(j1 - j0, a.Y, a.logC, 16, 16u);
-        if (int rc = allow_lds(reinterpret_cast<const void*>(&k_m_list<16, 1024>), lds16)) return rc;
-        hipLaunchKernelGGL((k_m_list<16, 1024>), dim3(blocks), dim3(1024), lds16, st, a, j0, j1);
+        if (int rc = launch_kernel(&k_m_list<16, 1024>, blocks, 1024u, lds16, st, a, j0, j1)) return rc;
         BAMM_HIP(hipGetLastError());
         return BAMM_OK;
     }
     const size_t lds = m_list_lds_bytes(j1 - j0, a.Y, a.logC, kMClasses[mclass], threads / 64u);
     if (lds > 160 * 1024 || j1 <= j0) { set_error("bad list M slice [%u,%u)", j0, j1); return BAMM_ERR_UNSUPPORTED; }
-    switch (mclass) {
-#define X(idx, M, T)                                                                                   \
-    case idx:                                                                                          \
-        if (int rc = allow_lds(reinterpret_cast<const void*>(&k_m_list<M, T>), lds)) return rc;        \
-        hipLaunchKernelGGL((k_m_list<M, T>), dim3(blocks), dim3(threads), lds, st, a, j0, j1);         \
-        break;
-        BAMM_FOR_EACH_MCLASS(X)
-#undef X
-        default: set_error("no kernel for M class %d", mclass); return BAMM_ERR_UNSUPPORTED;
-    }
+    if (int rc = with_mclass(mclass, [&](auto M, auto T) { return launch_kernel(&k_m_list<M, T>, blocks, threads, lds, st, a, j0, j1); }))
+        return rc;
     BAMM_HIP(hipGetLastError());
     return BAMM_OK;
 }
@@ -923,18 +891,8 @@ int launch_score(int mclass, const ScoreKernelArgs& a, uint32_t blocks, uint32_t
         set_error("bad launch geometry %u x %u for M class %d", blocks, threads, mclass);
         return BAMM_ERR_ARG;
     }
-    switch (mclass) {
-#define X(idx, M, T)                                                                                   \
-    case idx:                                                                                          \
-        if (int rc = allow_lds(reinterpret_cast<const void*>(&k_score<M, T>), lds)) return rc;                 \
-        hipLaunchKernelGGL((k_score<M, T>), dim3(blocks), dim3(threads), lds, st, a);                  \
-        break;
-        BAMM_FOR_EACH_MCLASS(X)
-#undef X
-        default:
-            set_error("no kernel for M class %d", mclass);
-            return BAMM_ERR_UNSUPPORTED;
-    }
+    if (int rc = with_mclass(mclass, [&](auto M, auto T) { return launch_kernel(&k_score<M, T>, blocks, threads, lds, st, a); }))
+        return rc;
     BAMM_HIP(hipGetLastError());
     return BAMM_OK;
 }

@@ -562,20 +562,32 @@ __global__ void __launch_bounds__(THREADS) k_em_mix(GrpKernelArgs ga) {
 template <int M, int A, int NQ, int THREADS>
 int launch_mix_variant(bool accum, bool write_r, const GrpKernelArgs& a, uint32_t blocks, hipStream_t st) {
     const size_t lds = a.g.lds_bytes;
-    int rc;
-    if (write_r) {
-        if ((rc = allow_lds(reinterpret_cast<const void*>(&k_em_mix<M, A, NQ, false, true, THREADS>), lds))) return rc;
-        if (blocks == kPrimeOnly) return prime_kernel(reinterpret_cast<const void*>(&k_em_mix<M, A, NQ, false, true, THREADS>));
-        hipLaunchKernelGGL((k_em_mix<M, A, NQ, false, true, THREADS>), dim3(blocks), dim3(THREADS), lds, st, a);
-    } else if (accum) {
-        if ((rc = allow_lds(reinterpret_cast<const void*>(&k_em_mix<M, A, NQ, true, false, THREADS>), lds))) return rc;
-        if (blocks == kPrimeOnly) return prime_kernel(reinterpret_cast<const void*>(&k_em_mix<M, A, NQ, true, false, THREADS>));
-        hipLaunchKernelGGL((k_em_mix<M, A, NQ, true, false, THREADS>), dim3(blocks), dim3(THREADS), lds, st, a);
-    } else {
-        if ((rc = allow_lds(reinterpret_cast<const void*>(&k_em_mix<M, A, NQ, false, false, THREADS>), lds))) return rc;
-        if (blocks == kPrimeOnly) return prime_kernel(reinterpret_cast<const void*>(&k_em_mix<M, A, NQ, false, false, THREADS>));
-        hipLaunchKernelGGL((k_em_mix<M, A, NQ, false, false, THREADS>), dim3(blocks), dim3(THREADS), lds, st, a);
+    if (write_r) return launch_kernel(&k_em_mix<M, A, NQ, false, true, THREADS>, blocks, THREADS, lds, st, a);
+    if (accum) return launch_kernel(&k_em_mix<M, A, NQ, true, false, THREADS>, blocks, THREADS, lds, st, a);
+    return launch_kernel(&k_em_mix<M, A, NQ, false, false, THREADS>, blocks, THREADS, lds, st, a);
+}
+
+// the launcher of the translation unit for A wide groups (grouped_mix.hip: A = 2, grouped_mix1.hip: A = 1); arguments
+// checked by launch_em_grp.  The planner keeps the narrow groups within one quad (mix_geometry: more of them lost to the
+// uniform rows), so only NQ = 1 is instantiated.
+template <int A>
+int launch_mix(int mclass, bool accum, bool write_r, const GrpKernelArgs& a, uint32_t blocks, uint32_t threads, hipStream_t st) {
+    if (threads != grp_max_threads(kMClasses[mclass]) || a.g.mixA != (uint32_t)A || a.g.Tq != 1u) {
+        set_error("mixed-row kernel: bad launch (%u threads, A=%u, %u quads)", threads, a.g.mixA, a.g.Tq);
+        return BAMM_ERR_ARG;
     }
+    int rc = BAMM_ERR_UNSUPPORTED;
+    switch (mclass) {
+        case 3: rc = launch_mix_variant<4, A, 1, 1024>(accum, write_r, a, blocks, st); break;
+        case 4: rc = launch_mix_variant<5, A, 1, 1024>(accum, write_r, a, blocks, st); break;
+        case 5: rc = launch_mix_variant<6, A, 1, 1024>(accum, write_r, a, blocks, st); break;
+        case 6: rc = launch_mix_variant<7, A, 1, 1024>(accum, write_r, a, blocks, st); break;
+        case 7: rc = launch_mix_variant<8, A, 1, 1024>(accum, write_r, a, blocks, st); break;
+        case 8: rc = launch_mix_variant<10, A, 1, 768>(accum, write_r, a, blocks, st); break;
+        default: set_error("no mixed-row kernel for M class %d", mclass);
+    }
+    if (rc) return rc;
+    BAMM_HIP(hipGetLastError());
     return BAMM_OK;
 }
 

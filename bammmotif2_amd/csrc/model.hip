@@ -96,12 +96,11 @@ __global__ void __launch_bounds__(1024) k_update(UpdateArgs a) {
     const uint32_t K = a.K, W = a.W;
     const uint32_t YK = 1u << (2 * (K + 1));
     const uint32_t tid = threadIdx.x, nt = blockDim.x;
-    auto voff = [W](uint32_t k) { return (size_t)W * (((size_t(1) << (2 * (k + 1))) - 4) / 3); };
     float* const n = a.n;                                  // all orders, flat [k][y][j]
     float* const v = a.v;
 
     // order-K counts from the (all-reduced) integer accumulator, which is left zeroed for the next pass
-    float* nK = n + voff(K);
+    float* nK = n + v_off(K, W);
     if (tid == 3) stat3[3] = 0.0;
     for (uint32_t i = tid; i < YK * W; i += nt) {
         nK[i] = (float)((double)a.acc[i] * a.count_unit);
@@ -118,8 +117,8 @@ __global__ void __launch_bounds__(1024) k_update(UpdateArgs a) {
     __syncthreads();
     // EM.cpp:247-254: n[k-1][y mod 4^k][j] += n[k][y][j], y ascending (same float order)
     for (uint32_t k = K; k > 0; k--) {
-        const float* nk = n + voff(k);
-        float* nk1 = n + voff(k - 1);
+        const float* nk = n + v_off(k, W);
+        float* nk1 = n + v_off(k - 1, W);
         const uint32_t Yk = 1u << (2 * k);                 // rows of order k-1
         for (uint32_t i = tid; i < Yk * W; i += nt) {
             const uint32_t y2 = i / W, j = i % W;
@@ -144,10 +143,10 @@ __global__ void __launch_bounds__(1024) k_update(UpdateArgs a) {
     __syncthreads();
     // Motif.h:121-135: orders 1..K
     for (uint32_t k = 1; k <= K; k++) {
-        const float* nk = n + voff(k);
-        const float* nk1 = n + voff(k - 1);
-        float* vk = v + voff(k);
-        const float* vk1 = v + voff(k - 1);
+        const float* nk = n + v_off(k, W);
+        const float* nk1 = n + v_off(k - 1, W);
+        float* vk = v + v_off(k, W);
+        const float* vk1 = v + v_off(k - 1, W);
         const float* Ak = a.A + (size_t)k * W;
         const uint32_t Yk1 = 1u << (2 * (k + 1)), Yk = 1u << (2 * k);
         for (uint32_t i = tid; i < Yk1 * W; i += nt) {
@@ -156,7 +155,7 @@ __global__ void __launch_bounds__(1024) k_update(UpdateArgs a) {
             float nv;
             if (j < k) nv = vk1[(size_t)y2 * W + j];
             else nv = (nk[i] + Ak[j] * vk1[(size_t)y2 * W + j]) / (nk1[(size_t)yk * W + j - 1] + Ak[j]);
-            if (k == K) diff += (double)fabsf(nv - a.v[voff(K) + i]);
+            if (k == K) diff += (double)fabsf(nv - a.v[v_off(K, W) + i]);
             vk[i] = nv;
         }
         __syncthreads();
@@ -179,7 +178,7 @@ __global__ void __launch_bounds__(1024) k_update(UpdateArgs a) {
     // next E-step's odds table (Motif.cpp:485-494)
     {
         const uint32_t Ys = YK + 1u, Yb = 1u << (2 * (a.Kbg + 1));
-        const float* vK = v + voff(K);
+        const float* vK = v + v_off(K, W);
         const float* b = a.vbg + (((size_t)Yb - 4) / 3);
         for (uint32_t i = tid; i < W * Ys; i += nt) {
             const uint32_t j = i / Ys, y = i % Ys;
@@ -187,40 +186,8 @@ __global__ void __launch_bounds__(1024) k_update(UpdateArgs a) {
         }
     }
     if (tid == 0) {
-        const double llh = stat3[3] != 0.0 ? (double)NAN : stat3[0], sum_r = stat3[1];
-        const double nseq = a.n_seqs_override > 0.0 ? a.n_seqs_override : stat3[2];
-        const uint32_t it = *a.iteration + 1u;
-        *a.iteration = it;
-        float q = *a.q;
-        if (a.optimize_q)                                  // EM.cpp:515; the host applies EM.cpp:99's `iteration <= 5`
-            q = (float)((nseq - sum_r + 1.0) / (nseq + 2.0));
-        *a.q_out = q;
-        if (a.stop != nullptr) {                           // EM.cpp:117-118
-            const float llh_prev = a.llh_prev_from_status ? *a.llh_in : a.llh_prev;
-            if ((float)v_diff < a.epsilon || ((float)llh - llh_prev < 0 && a.opt_iteration > 10u)) *a.stop = 1u;
-        }
-        if (a.llh_out != nullptr) *a.llh_out = (float)llh;
-        a.status[0] = (float)llh;
-        a.status[1] = (float)v_diff;
-        a.status[2] = q;
-        a.status[3] = (float)it;
-        a.status[4] = (float)sum_r;
-        a.status[5] = (float)nseq;
-        if (a.status_mirror != nullptr) {
-            // six self-validating 8-byte words {pass number | float bits}: optimize() polls them instead of waiting for an event on
-            // the stream (4 us of stream time per pass); no fence between the words -- each carries its own tag (RCCL's LL idea)
-            {
-                const float f6[6] = {(float)llh, (float)v_diff, q, (float)it, (float)sum_r, (float)nseq};
-                const unsigned long long tag = (unsigned long long)a.opt_iteration << 32;
-#pragma unroll
-                for (int i = 0; i < 6; i++) __hip_atomic_store(a.status_mirror + i, tag | (unsigned long long)__float_as_uint(f6[i]), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-            }
-        }
-        if (a.trace && it - 1u < a.trace_cap) {
-            a.trace[(size_t)(it - 1u) * 3 + 0] = (float)llh;
-            a.trace[(size_t)(it - 1u) * 3 + 1] = (float)v_diff;
-            a.trace[(size_t)(it - 1u) * 3 + 2] = q;
-        }
+        const PassStats st = pass_stats(stat3, a);
+        publish_pass(a, st, (float)v_diff, next_q(a, st, *a.q), stop_fires(a, (float)v_diff, st.llh, llh_before(a)));
     }
     }
 }
@@ -233,18 +200,6 @@ __global__ void __launch_bounds__(1024) k_update(UpdateArgs a) {
 //   k_update_model   per cell of every order the v chain from order 0 up (Motif.h:100-135, the expressions of
 //                    model_update_lds), v_diff (per-block fp64 partials, summed in block order by the last block to
 //                    draw a ticket: the same bits every run), the odds table; the accumulator is cleared here
-// sum of the 4^D leaves under `row` in the reference's nesting: each level adds its four children in ascending order
-template <int D, class Leaf>
-__device__ __forceinline__ float count_tree(uint32_t row, uint32_t stride, const Leaf& leaf) {
-    if constexpr (D == 0) return leaf(row);
-    else {
-        float s = 0.0f;
-#pragma unroll
-        for (uint32_t d = 0; d < 4; d++) s += count_tree<D - 1>(row + d * stride, stride * 4u, leaf);
-        return s;
-    }
-}
-
 // One band of orders: the cells of orders k_src-1 and k_src-2 summed from order k_src (FROM_ACC: the accumulator,
 // k_src == K, whose own cells are converted here too; else the floats the band before wrote): at most 16 loads per
 // thread, all issued before the first add.
@@ -252,14 +207,13 @@ template <bool FROM_ACC>
 __global__ void __launch_bounds__(256) k_update_counts(UpdateArgs a, uint32_t k_src) {
     if (a.stop != nullptr && *a.stop != 0u) return;      // optimize(): the stop rule fired in an earlier pass
     const uint32_t W = a.W;
-    auto voff = [W](uint32_t k) { return (size_t)W * (((size_t(1) << (2 * (k + 1))) - 4) / 3); };
     const uint32_t k_lo = k_src > 2u ? k_src - 2u : 0u;
-    const size_t first = voff(k_lo), last = voff(FROM_ACC ? k_src + 1u : k_src);
-    const float* const src = a.n + voff(k_src);
+    const size_t first = v_off(k_lo, W), last = v_off(FROM_ACC ? k_src + 1u : k_src, W);
+    const float* const src = a.n + v_off(k_src, W);
     for (size_t c = first + (size_t)blockIdx.x * blockDim.x + threadIdx.x; c < last; c += (size_t)gridDim.x * blockDim.x) {
         uint32_t k = k_lo;
-        while (c >= voff(k + 1)) k++;
-        const uint32_t i = (uint32_t)(c - voff(k)), y = i / W, j = i % W;
+        while (c >= v_off(k + 1, W)) k++;
+        const uint32_t i = (uint32_t)(c - v_off(k, W)), y = i / W, j = i % W;
         auto leaf = [&](uint32_t row) {
             if constexpr (FROM_ACC) return (float)((double)a.acc[(size_t)row * W + j] * a.count_unit);
             else return src[(size_t)row * W + j];
@@ -276,7 +230,6 @@ __global__ void __launch_bounds__(256) k_update_model(UpdateArgs a) {
     __shared__ uint32_t my_ticket;
     const uint32_t K = a.K, W = a.W;
     const uint32_t YK = 1u << (2 * (K + 1)), Ys = YK + 1u, Yb = 1u << (2 * (a.Kbg + 1));
-    auto voff = [W](uint32_t k) { return (size_t)W * (((size_t(1) << (2 * (k + 1))) - 4) / 3); };
     const float* const n = a.n;
     const float* const b = a.vbg + (((size_t)Yb - 4) / 3);
     constexpr uint32_t kMaxK = 10;                           // bamm_em_create's limit
@@ -295,10 +248,10 @@ __global__ void __launch_bounds__(256) k_update_model(UpdateArgs a) {
             if (kk > K || j < kk) continue;
             const uint32_t ykk = y & ((1u << (2 * (kk + 1))) - 1u);
             Ak[kk] = a.A[kk * W + j];
-            num[kk] = n[voff(kk) + (size_t)ykk * W + j];
-            den[kk] = n[voff(kk - 1) + (size_t)(ykk >> 2) * W + j - 1u];
+            num[kk] = n[v_off(kk, W) + (size_t)ykk * W + j];
+            den[kk] = n[v_off(kk - 1, W) + (size_t)(ykk >> 2) * W + j - 1u];
         }
-        const float old = a.v[voff(K) + i];                  // before the stores: v is updated in place
+        const float old = a.v[v_off(K, W) + i];                  // before the stores: v is updated in place
         const float bgK = b[y % Yb];
         float val = (n0[y & 3u] + Ak[0] * bg0) / (((n0[0] + n0[1]) + n0[2]) + n0[3] + Ak[0]);
         if (K > 0u && y < 4u) a.v[i] = val;                  // the lower orders' cells ride on the rows that spell them
@@ -306,10 +259,10 @@ __global__ void __launch_bounds__(256) k_update_model(UpdateArgs a) {
         for (uint32_t kk = 1; kk <= kMaxK; kk++) {
             if (kk > K) continue;
             if (j >= kk) val = (num[kk] + Ak[kk] * val) / (den[kk] + Ak[kk]);
-            if (kk < K && y < (1u << (2 * (kk + 1)))) a.v[voff(kk) + i] = val;
+            if (kk < K && y < (1u << (2 * (kk + 1)))) a.v[v_off(kk, W) + i] = val;
         }
         diff += (double)fabsf(val - old);
-        a.v[voff(K) + i] = val;
+        a.v[v_off(K, W) + i] = val;
         a.s[(size_t)j * Ys + y] = val / bgK;                 // Motif.cpp:485-494
         a.acc[i] = 0ll;                                      // consumed by k_update_counts
         if (a.acc_zero != nullptr) a.acc_zero[i] = 0ll;
@@ -350,36 +303,8 @@ __global__ void __launch_bounds__(256) k_update_model(UpdateArgs a) {
     const long long x0 = st[0], x1 = st[1], x2 = st[2];
     st[0] = 0ll; st[1] = 0ll; st[2] = 0ll;
     if (a.acc_zero != nullptr) { a.acc_zero[(size_t)YK * W] = 0ll; a.acc_zero[(size_t)YK * W + 1] = 0ll; a.acc_zero[(size_t)YK * W + 2] = 0ll; }
-    const double llh = stat_bad(x2) ? (double)NAN : (double)x0 / kLlhScale, sum_r = (double)x1 / kSumrScale;
-    const double nseq = a.n_seqs_override > 0.0 ? a.n_seqs_override : stat_nseq(x2);
-    const uint32_t it = *a.iteration + 1u;
-    *a.iteration = it;
-    float q = *a.q;
-    if (a.optimize_q)                                      // EM.cpp:515; the host applies EM.cpp:99's `iteration <= 5`
-        q = (float)((nseq - sum_r + 1.0) / (nseq + 2.0));
-    *a.q_out = q;
-    if (a.stop != nullptr) {                               // EM.cpp:117-118
-        const float llh_prev = a.llh_prev_from_status ? *a.llh_in : a.llh_prev;
-        if ((float)v_diff < a.epsilon || ((float)llh - llh_prev < 0 && a.opt_iteration > 10u)) *a.stop = 1u;
-    }
-    if (a.llh_out != nullptr) *a.llh_out = (float)llh;
-    a.status[0] = (float)llh; a.status[1] = (float)v_diff; a.status[2] = q; a.status[3] = (float)it;
-    a.status[4] = (float)sum_r; a.status[5] = (float)nseq;
-    if (a.status_mirror != nullptr) {
-        // six self-validating 8-byte words {pass number | float bits}: optimize() polls them instead of waiting for an event on
-        // the stream (4 us of stream time per pass); no fence between the words -- each carries its own tag (RCCL's LL idea)
-        {
-            const float f6[6] = {(float)llh, (float)v_diff, q, (float)it, (float)sum_r, (float)nseq};
-            const unsigned long long tag = (unsigned long long)a.opt_iteration << 32;
-#pragma unroll
-            for (int i = 0; i < 6; i++) __hip_atomic_store(a.status_mirror + i, tag | (unsigned long long)__float_as_uint(f6[i]), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        }
-    }
-    if (a.trace && it - 1u < a.trace_cap) {
-        a.trace[(size_t)(it - 1u) * 3 + 0] = (float)llh;
-        a.trace[(size_t)(it - 1u) * 3 + 1] = (float)v_diff;
-        a.trace[(size_t)(it - 1u) * 3 + 2] = q;
-    }
+    const PassStats stats = pass_stats(x0, x1, x2, a.n_seqs_override);
+    publish_pass(a, stats, (float)v_diff, next_q(a, stats, *a.q), stop_fires(a, (float)v_diff, stats.llh, llh_before(a)));
 }
 
 // EStep() alone: publish the statistics and clear them (the counts part was not touched)

@@ -4,7 +4,7 @@
 // (file:line relative to /root/reference/src).
 //
 // Two callers run the SAME code (same float formulas in the same order: bit-identical models):
-//   * k_update<true> (kernels.hip): one block after the pass's all-reduce, the accumulator consumed and zeroed;
+//   * k_update<true> (model.hip): one block after the pass's all-reduce, the accumulator consumed and zeroed;
 //   * the block prologue of the NEXT pass's first sequence kernel (k_em_mix / k_em_grp, "fused update"): every
 //     block recomputes the <= 2048-cell update from the all-reduced accumulator of the previous pass into its own
 //     LDS -- 10 KB read through L2 and a few hundred cycles of LDS arithmetic instead of a kernel launch between
@@ -109,14 +109,74 @@ __device__ __forceinline__ void peer_allreduce_tail(PeerArgsK pk, long long* acc
 
 // sum of the 4^D leaves under `row` in the reference's nesting (EM.cpp:247-254): each level adds its four children in
 // ascending order, from 0.0f; the loads of a cell are independent and issued together
-template <int D>
-__device__ __forceinline__ float update_count_tree(const float* nK, uint32_t W, uint32_t j, uint32_t row, uint32_t stride) {
-    if constexpr (D == 0) return nK[(size_t)row * W + j];
+template <int D, class Leaf>
+__device__ __forceinline__ float count_tree(uint32_t row, uint32_t stride, const Leaf& leaf) {
+    if constexpr (D == 0) return leaf(row);
     else {
         float s = 0.0f;
 #pragma unroll
-        for (uint32_t d = 0; d < 4; d++) s += update_count_tree<D - 1>(nK, W, j, row + d * stride, stride * 4u);
+        for (uint32_t d = 0; d < 4; d++) s += count_tree<D - 1>(row + d * stride, stride * 4u, leaf);
         return s;
+    }
+}
+
+// ---- the end of a pass in k_update<false> and k_update_model; model_update_lds writes the same out in place ----
+// The accumulator's three statistics words decoded: llh (NaN when some block's statistics were not finite), sum_r, n_seqs.
+struct PassStats { double llh, sum_r, nseq; };
+
+// stat4: the words as k_update<false> decodes them, a lane each, into LDS; stat4[3] != 0: not finite
+__device__ __forceinline__ PassStats pass_stats(const double* stat4, const UpdateArgs& a) {
+    return {stat4[3] != 0.0 ? (double)NAN : stat4[0], stat4[1], a.n_seqs_override > 0.0 ? a.n_seqs_override : stat4[2]};
+}
+__device__ __forceinline__ PassStats pass_stats(long long x0, long long x1, long long x2, double n_seqs_override) {
+    return {stat_bad(x2) ? (double)NAN : (double)x0 / kLlhScale, (double)x1 / kSumrScale,
+            n_seqs_override > 0.0 ? n_seqs_override : stat_nseq(x2)};
+}
+
+// EM.cpp:515; the host applies EM.cpp:99's `iteration <= 5`
+__device__ __forceinline__ float next_q(const UpdateArgs& a, const PassStats& st, float q_in) {
+    float q = q_in;
+    if (a.optimize_q) q = (float)((st.nseq - st.sum_r + 1.0) / (st.nseq + 2.0));
+    return q;
+}
+
+// the likelihood the stop rule compares against; read before the writer stores anything
+__device__ __forceinline__ float llh_before(const UpdateArgs& a) {
+    return (a.stop != nullptr && a.llh_prev_from_status) ? *a.llh_in : a.llh_prev;
+}
+
+// EM.cpp:117-118 (false when a.stop == nullptr); v_diff here and in publish_pass(): the fp64 sum, rounded by the caller
+__device__ __forceinline__ bool stop_fires(const UpdateArgs& a, float v_diff, double llh, float llh_prev) {
+    bool fired = false;
+    if (a.stop != nullptr) fired = v_diff < a.epsilon || ((float)llh - llh_prev < 0 && a.opt_iteration > 10u);
+    return fired;
+}
+
+// one thread of the writer: iteration, q, llh, the stop flag, status, the status mirror optimize() polls, the trace row
+__device__ __forceinline__ void publish_pass(const UpdateArgs& a, const PassStats& st, float v_diff, float q, bool fired) {
+    const uint32_t it = *a.iteration + 1u;
+    *a.iteration = it;
+    *a.q_out = q;
+    if (a.llh_out != nullptr) *a.llh_out = (float)st.llh;
+    if (fired) *a.stop = 1u;
+    a.status[0] = (float)st.llh;
+    a.status[1] = v_diff;
+    a.status[2] = q;
+    a.status[3] = (float)it;
+    a.status[4] = (float)st.sum_r;
+    a.status[5] = (float)st.nseq;
+    if (a.status_mirror != nullptr) {
+        // six self-validating 8-byte words {pass number | float bits}: optimize() polls them instead of waiting for an event on
+        // the stream (4 us of stream time per pass); no fence between the words -- each carries its own tag (RCCL's LL idea)
+        const float f6[6] = {(float)st.llh, v_diff, q, (float)it, (float)st.sum_r, (float)st.nseq};
+        const unsigned long long tag = (unsigned long long)a.opt_iteration << 32;
+#pragma unroll
+        for (int i = 0; i < 6; i++) __hip_atomic_store(a.status_mirror + i, tag | (unsigned long long)__float_as_uint(f6[i]), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+    if (a.trace && it - 1u < a.trace_cap) {
+        a.trace[(size_t)(it - 1u) * 3 + 0] = (float)st.llh;
+        a.trace[(size_t)(it - 1u) * 3 + 1] = v_diff;
+        a.trace[(size_t)(it - 1u) * 3 + 2] = q;
     }
 }
 
@@ -139,8 +199,7 @@ __device__ __forceinline__ UpdateOut model_update_lds(const UpdateArgs& a, unsig
     const uint32_t K = a.K, W = a.W;
     const uint32_t YK = 1u << (2 * (K + 1));
     const uint32_t tid = threadIdx.x, nt = blockDim.x;
-    auto voff = [W](uint32_t k) { return (size_t)W * (((size_t(1) << (2 * (k + 1))) - 4) / 3); };
-    const size_t vsz = voff(K + 1);
+    const size_t vsz = v_off(K + 1, W);
     const uint32_t nA = (K + 1u) * W, nB = ((1u << (2 * (a.Kbg + 2))) - 4u) / 3u;   // A[k][j]; vbg orders 0..Kbg
     float* const n = reinterpret_cast<float*>(upd);                  // all orders, flat [k][y][j]
     float* const Al = n + vsz;                                       // [(K+1) * W]
@@ -156,13 +215,13 @@ __device__ __forceinline__ UpdateOut model_update_lds(const UpdateArgs& a, unsig
     // else instead of inside the chains (a global round trip in phase C: 1 us)
     float vo0 = 0.0f, vo1 = 0.0f;
     if (want_diff) {
-        if (tid < YK * W) vo0 = v_old[voff(K) + tid];
-        if (tid + nt < YK * W) vo1 = v_old[voff(K) + tid + nt];
+        if (tid < YK * W) vo0 = v_old[v_off(K, W) + tid];
+        if (tid + nt < YK * W) vo1 = v_old[v_off(K, W) + tid + nt];
     }
     if (tid == 0) stat3[3] = 0.0;
     const float q_in = *a.q;                                         // issued with the other loads of the update, used last
-    const float llh_before = (a.stop != nullptr && a.llh_prev_from_status) ? *a.llh_in : a.llh_prev;
-    float* nK = n + voff(K);
+    const float llh_prev = llh_before(a);
+    float* nK = n + v_off(K, W);
     for (uint32_t i = tid; i < YK * W; i += nt) {
         nK[i] = (float)((double)acc[i] * a.count_unit);
         if (CONSUME) acc[i] = 0ll;
@@ -185,20 +244,21 @@ __device__ __forceinline__ UpdateOut model_update_lds(const UpdateArgs& a, unsig
     // tables fit LDS for K <= 4 only), each level summed from 0.0f upwards as the reference's += does
     // (all lower orders as ONE index space, a cell per thread and round: order after order the first threads walked
     // 16 + 4 dependent reads while the others waited -- 1.6 us of the fused update's 6, tools/phase_clock.py)
-    for (uint32_t i = tid; i < (uint32_t)voff(K); i += nt) {
+    for (uint32_t i = tid; i < (uint32_t)v_off(K, W); i += nt) {
         uint32_t k = 0;
-        while (i >= voff(k + 1)) k++;
-        const uint32_t c = i - (uint32_t)voff(k), y = c / W, j = c % W;
+        while (i >= v_off(k + 1, W)) k++;
+        const uint32_t c = i - (uint32_t)v_off(k, W), y = c / W, j = c % W;
         const uint32_t Yk = 1u << (2 * (k + 1));
+        auto leaf = [&](uint32_t row) { return nK[(size_t)row * W + j]; };
         float r;
         if constexpr (!CONSUME) {                                    // fused into a sequence kernel: planned for K <= 2 only
-            r = (K - k == 1u) ? update_count_tree<1>(nK, W, j, y, Yk) : update_count_tree<2>(nK, W, j, y, Yk);
+            r = (K - k == 1u) ? count_tree<1>(y, Yk, leaf) : count_tree<2>(y, Yk, leaf);
         } else {
             switch (K - k) {
-                case 1: r = update_count_tree<1>(nK, W, j, y, Yk); break;
-                case 2: r = update_count_tree<2>(nK, W, j, y, Yk); break;
-                case 3: r = update_count_tree<3>(nK, W, j, y, Yk); break;
-                default: r = update_count_tree<4>(nK, W, j, y, Yk); break;
+                case 1: r = count_tree<1>(y, Yk, leaf); break;
+                case 2: r = count_tree<2>(y, Yk, leaf); break;
+                case 3: r = count_tree<3>(y, Yk, leaf); break;
+                default: r = count_tree<4>(y, Yk, leaf); break;
             }
         }
         n[i] = r;
@@ -218,8 +278,8 @@ __device__ __forceinline__ UpdateOut model_update_lds(const UpdateArgs& a, unsig
         for (uint32_t kk = 1; kk <= k; kk++) {
             if (j < kk) continue;                                    // the copy of the lower order's value
             const uint32_t ykk = y & ((1u << (2 * (kk + 1))) - 1u);
-            const float* nkk = n + voff(kk);
-            const float* nk1 = n + voff(kk - 1);
+            const float* nkk = n + v_off(kk, W);
+            const float* nk1 = n + v_off(kk - 1, W);
             const float Akj = Al[kk * W + j];
             val = (nkk[(size_t)ykk * W + j] + Akj * val) / (nk1[(size_t)(ykk >> 2) * W + j - 1u] + Akj);
         }
@@ -235,8 +295,8 @@ __device__ __forceinline__ UpdateOut model_update_lds(const UpdateArgs& a, unsig
             const uint32_t y = i / W, j = i % W;
             const float nv = v_cell(k, y, j);
             if (k == K && want_diff)                                 // the old value was read in phase A: k_update updates v in place
-                diff += (double)fabsf(nv - (i < nt ? vo0 : (i < 2u * nt ? vo1 : v_old[voff(K) + i])));
-            if (writer) { a.v[voff(k) + i] = nv; a.n[voff(k) + i] = n[voff(k) + i]; }
+                diff += (double)fabsf(nv - (i < nt ? vo0 : (i < 2u * nt ? vo1 : v_old[v_off(K, W) + i])));
+            if (writer) { a.v[v_off(k, W) + i] = nv; a.n[v_off(k, W) + i] = n[v_off(k, W) + i]; }
             if (k == K) {
                 const float sv = nv / b[y % Yb];                     // Motif.cpp:485-494
                 if (s_lds != nullptr) s_lds[(size_t)j * Ys + y] = sv;
@@ -260,17 +320,16 @@ __device__ __forceinline__ UpdateOut model_update_lds(const UpdateArgs& a, unsig
         __syncthreads();
         for (uint32_t w = 0; w < (nt + 63u) / 64u; w++) v_diff += shd[w];      // same order in every thread
     }
+    // The end of the pass as pass_stats(), next_q(), stop_fires() and publish_pass() do it for the other two forms, written
+    // out: called here, the helpers change how k_em_grp is scheduled.  A change to one is a change to the other.
     UpdateOut out;
     const double llh = stat3[3] != 0.0 ? (double)NAN : stat3[0], sum_r = stat3[1];
     const double nseq = a.n_seqs_override > 0.0 ? a.n_seqs_override : stat3[2];
     float q = q_in;
-    if (a.optimize_q)                                                // EM.cpp:515; the host applies EM.cpp:99's `iteration <= 5`
-        q = (float)((nseq - sum_r + 1.0) / (nseq + 2.0));
+    if (a.optimize_q) q = (float)((nseq - sum_r + 1.0) / (nseq + 2.0));   // EM.cpp:515
     out.q = q;
     out.fired = false;
-    if (a.stop != nullptr) {                                         // EM.cpp:117-118
-        out.fired = (float)v_diff < a.epsilon || ((float)llh - llh_before < 0 && a.opt_iteration > 10u);
-    }
+    if (a.stop != nullptr) out.fired = (float)v_diff < a.epsilon || ((float)llh - llh_prev < 0 && a.opt_iteration > 10u);
     if (writer && tid == 0) {
         const uint32_t it = *a.iteration + 1u;
         *a.iteration = it;
@@ -284,14 +343,10 @@ __device__ __forceinline__ UpdateOut model_update_lds(const UpdateArgs& a, unsig
         a.status[4] = (float)sum_r;
         a.status[5] = (float)nseq;
         if (a.status_mirror != nullptr) {
-            // six self-validating 8-byte words {pass number | float bits}: optimize() polls them instead of waiting for an event on
-            // the stream (4 us of stream time per pass); no fence between the words -- each carries its own tag (RCCL's LL idea)
-            {
-                const float f6[6] = {(float)llh, (float)v_diff, q, (float)it, (float)sum_r, (float)nseq};
-                const unsigned long long tag = (unsigned long long)a.opt_iteration << 32;
+            const float f6[6] = {(float)llh, (float)v_diff, q, (float)it, (float)sum_r, (float)nseq};
+            const unsigned long long tag = (unsigned long long)a.opt_iteration << 32;
 #pragma unroll
-                for (int i = 0; i < 6; i++) __hip_atomic_store(a.status_mirror + i, tag | (unsigned long long)__float_as_uint(f6[i]), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-            }
+            for (int i = 0; i < 6; i++) __hip_atomic_store(a.status_mirror + i, tag | (unsigned long long)__float_as_uint(f6[i]), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
         }
         if (a.trace && it - 1u < a.trace_cap) {
             a.trace[(size_t)(it - 1u) * 3 + 0] = (float)llh;
