@@ -287,6 +287,29 @@ struct ScoreKernelArgs {
 };
 
 
+// ---- window p-values on the device (occ.hip; ScoreSeqSet.cpp:70-126) ----
+struct OccCand {                 // a positive window the host has to look at
+    unsigned long long window;   // index into the concatenated L-W+1 scores of the positive set
+    float    score;              // Sl
+    float    higher, lower;      // the sorted negatives next to it: neg[negN - FPl - 1], neg[negN - FPl] (where the formula reads them)
+    uint32_t fp;                 // FPl: negatives scoring above Sl
+};
+struct OccRankArgs {
+    const float* pos;            // scores of the positive windows
+    uint64_t n_pos;
+    const float* neg;            // the negative windows' scores, ascending
+    uint32_t n_neg;              // 1 .. 2^31 - 1
+    float    p_cutoff;
+    uint32_t expf_branch;        // fabs(lambda) > eps: windows with FPl < 10 take the branch only the host can evaluate
+    OccCand* out;
+    unsigned long long cap;      // entries `out` holds; candidates beyond it are counted, not stored
+    unsigned long long* count;   // zeroed by the caller
+};
+// keys-only ascending sort of n floats in place (`alt`: n words of scratch, `hist`: 256 * blocks words); -0 comes back as +0
+uint32_t occ_sort_blocks(uint32_t n, uint32_t num_cus);
+int launch_occ_sort(float* keys, uint32_t* alt, uint32_t* hist, uint32_t n, uint32_t blocks, hipStream_t st);
+int launch_occ_rank(const OccRankArgs& a, uint32_t blocks, hipStream_t st);
+
 struct MaskSelect {              // device state of the radix select (EM.cpp:329-343)
     double   pos_count;          // number of windows (all ranks)
     double   rank;               // remaining 0-based rank in the descending order

@@ -1,6 +1,6 @@
 // The handles behind the C ABI (include/bamm_em.h) and the helpers their host units share: ctx.cpp (contexts, staging,
 // scratch pool), seqs.cpp (resident sequence sets), plan.cpp (launch plan of an EM handle), em_pass.cpp (one pass, one
-// update, the all-reduce), em.cpp (the EM entry points) and score.cpp (the scorer).  Host units only -- no kernel includes it.
+// update, the all-reduce), em.cpp (the EM entry points), score.cpp (the scorer) and occurrences.cpp (window p-values).  Host units only -- no kernel includes it.
 //
 // Reference seam these replace: class EM (/root/reference/src/refinement/EM.h:11-69,
 // EM.cpp:7-259,505-527) and ScoreSeqSet::calcLogOdds (seq_scoring/ScoreSeqSet.cpp:25-67).
@@ -317,6 +317,18 @@ int xrec_for_group(bamm_seqs* s, uint32_t K, uint32_t G, ExcK* k, const ExcK::XR
 inline SeqView make_view(const bamm_seqs* s, const ExcK* exc, const uint32_t* idx, uint32_t count, const uint8_t* mask) {
     return SeqView{s->d_words, s->d_word_off, s->d_len, s->d_pos_off, exc->d_off, exc->d_exc, mask, idx, count};
 }
+
+// ---- score.cpp ----
+// ScoreSeqSet::calcLogOdds over a resident set, results left on the device in memory `tmp` owns: the log-odds table, the
+// per-bucket launches with their long-sequence / large-table fall-backs.  Arguments are the caller's to check.
+struct DeviceScores {
+    float* mops = nullptr;              // concatenated L-W+1 scores per sequence (want_mops), else null
+    float* zoops = nullptr;             // [n]
+    uint32_t* z = nullptr;              // [n]
+    std::vector<uint64_t> moff;         // [n+1] prefix sums of L-W+1
+};
+int score_on_device(bamm_ctx* c, bamm_seqs* s, const uint8_t* seq_mask, uint32_t K, uint32_t W, uint32_t bg_order, const float* v,
+                    const float* vbg, bool want_mops, bool pooled_mops, DevTemps& tmp, DeviceScores* out);
 
 // ---- plan.cpp ----
 uint32_t default_threads(const bamm_ctx* c, int mclass);

@@ -7,6 +7,62 @@
 
 using namespace bamm;
 
+namespace bamm {
+
+int score_on_device(bamm_ctx* c, bamm_seqs* s, const uint8_t* seq_mask, uint32_t K, uint32_t W, uint32_t bg_order, const float* v,
+                    const float* vbg, bool want_mops, bool pooled_mops, DevTemps& tmp, DeviceScores* out) {
+    const uint32_t Y = (uint32_t)ipow4(K + 1), Ys = Y + 1, Kbg = std::min(bg_order, K);
+    const uint32_t Yb = (uint32_t)ipow4(Kbg + 1);
+    // Motif::calculateLogS (Motif.cpp:471-483) with the host's logf, laid out [j][y] + neutral row
+    std::vector<float> tab((size_t)W * Ys, 0.0f);
+    const float* vK = v + v_offset(K, W);
+    const float* b = vbg + bg_offset(Kbg);
+    for (uint32_t y = 0; y < Y; y++)
+        for (uint32_t j = 0; j < W; j++)
+            tab[(size_t)j * Ys + y] = logf(vK[(size_t)y * W + j] + 1e-5f) - logf(b[y % Yb]);
+    std::vector<uint64_t>& moff = out->moff;
+    moff.assign(s->n + 1, 0);
+    for (uint64_t n = 0; n < s->n; n++) moff[n + 1] = moff[n] + (s->h_len[n] - W + 1);
+    hipStream_t st = c->stream;
+    ExcK* exc = nullptr;
+    int rc = exceptions_for_order(s, K, &exc);
+    if (rc) return rc;
+    float *d_tab = nullptr, *d_mops = nullptr, *d_zoops = nullptr;
+    uint64_t* d_moff = nullptr;
+    uint32_t* d_z = nullptr;
+    uint8_t* d_smask = nullptr;
+    if ((rc = tmp.upload(&d_tab, tab.data(), tab.size())) || (rc = tmp.upload(&d_moff, moff.data(), moff.size())) ||
+        (rc = tmp.alloc(&d_zoops, s->n)) || (rc = tmp.alloc(&d_z, s->n)) ||
+        (want_mops && (rc = pooled_mops ? tmp.scratch(&d_mops, (size_t)std::max<uint64_t>(1, moff[s->n])) : tmp.alloc(&d_mops, moff[s->n]))) ||
+        (seq_mask && (rc = tmp.upload(&d_smask, seq_mask, s->n)))) return rc;
+    if (seq_mask) {                                          // sequences outside the subset report zeros
+        hipError_t e = hipMemsetAsync(d_zoops, 0, s->n * sizeof(float), st);
+        if (e == hipSuccess) e = hipMemsetAsync(d_z, 0, s->n * sizeof(uint32_t), st);
+        if (e == hipSuccess && want_mops) e = hipMemsetAsync(d_mops, 0, moff[s->n] * sizeof(float), st);
+        if (e != hipSuccess) { set_error("hipMemsetAsync failed: %s", hipGetErrorString(e)); return BAMM_ERR_HIP; }
+    }
+    for (size_t bi = 0; bi < s->buckets.size() && !rc; bi++) {
+        const Bucket& bk = s->buckets[bi];
+        ScoreKernelArgs a{};
+        a.sv = make_view(s, exc, bk.d_idx, bk.count, d_smask);
+        a.K = K; a.W = W; a.Y = Y; a.s = d_tab; a.mops = d_mops; a.mops_off = d_moff; a.zoops = d_zoops; a.z = d_z;
+        // beyond the length classes, or a log-odds table beyond the LDS of a CU (orders >= 6 at usual widths): the
+        // window-by-window scorer reads the table from global memory, same sums in the same order
+        if (bk.mclass == kLongClass || (size_t)W * Ys * sizeof(float) > 160u * 1024u) {
+            rc = launch_long_score(a, std::min(bk.count, (uint32_t)std::max(1, c->num_cus) * 8u), st);
+            continue;
+        }
+        const uint32_t threads = default_threads(c, bk.mclass);
+        uint32_t blocks = default_blocks(c, threads);
+        blocks = std::max(1u, std::min(blocks, (bk.count + threads / 64u - 1) / (threads / 64u)));
+        rc = launch_score(bk.mclass, a, blocks, threads, st);
+    }
+    out->mops = d_mops; out->zoops = d_zoops; out->z = d_z;
+    return rc;
+}
+
+}  // namespace bamm
+
 extern "C" {
 
 int bamm_seed_from_pwm(bamm_ctx* c, bamm_seqs* s, uint32_t K, uint32_t W, const float* score, float q, const double* u,
@@ -62,58 +118,20 @@ int bamm_logodds_subset(bamm_ctx* c, bamm_seqs* s, const uint8_t* seq_mask, uint
     if (s->n && s->min_len < W) { set_error("a sequence is shorter than the motif (W=%u)", W); return BAMM_ERR_ARG; }
     if (s->n == 0) return BAMM_OK;
     BAMM_HIP(hipSetDevice(c->device));
-    const uint32_t Y = (uint32_t)ipow4(K + 1), Ys = Y + 1, Kbg = std::min(bg_order, K);
-    const uint32_t Yb = (uint32_t)ipow4(Kbg + 1);
-    // Motif::calculateLogS (Motif.cpp:471-483) with the host's logf, laid out [j][y] + neutral row
-    std::vector<float> tab((size_t)W * Ys, 0.0f);
-    const float* vK = v + v_offset(K, W);
-    const float* b = vbg + bg_offset(Kbg);
-    for (uint32_t y = 0; y < Y; y++)
-        for (uint32_t j = 0; j < W; j++)
-            tab[(size_t)j * Ys + y] = logf(vK[(size_t)y * W + j] + 1e-5f) - logf(b[y % Yb]);
-    std::vector<uint64_t> moff(s->n + 1, 0);
-    for (uint64_t n = 0; n < s->n; n++) moff[n + 1] = moff[n] + (s->h_len[n] - W + 1);
-    if (mops && mops_cap < moff[s->n]) { set_error("mops buffer too small"); return BAMM_ERR_ARG; }
-    hipStream_t st = c->stream;
-    ExcK* exc = nullptr;
-    int rc = exceptions_for_order(s, K, &exc);
-    if (rc) return rc;
-    float *d_tab = nullptr, *d_mops = nullptr, *d_zoops = nullptr;
-    uint64_t* d_moff = nullptr;
-    uint32_t* d_z = nullptr;
-    uint8_t* d_smask = nullptr;
+    if (mops) {
+        uint64_t windows = 0;
+        for (uint64_t n = 0; n < s->n; n++) windows += s->h_len[n] - W + 1;
+        if (mops_cap < windows) { set_error("mops buffer too small"); return BAMM_ERR_ARG; }
+    }
     DevTemps tmp(c);
-    if ((rc = tmp.upload(&d_tab, tab.data(), tab.size())) || (rc = tmp.upload(&d_moff, moff.data(), moff.size())) ||
-        (rc = tmp.alloc(&d_zoops, s->n)) || (rc = tmp.alloc(&d_z, s->n)) || (mops && (rc = tmp.alloc(&d_mops, moff[s->n]))) ||
-        (seq_mask && (rc = tmp.upload(&d_smask, seq_mask, s->n)))) return rc;
-    if (seq_mask) {                                          // sequences outside the subset report zeros
-        hipError_t e = hipMemsetAsync(d_zoops, 0, s->n * sizeof(float), st);
-        if (e == hipSuccess) e = hipMemsetAsync(d_z, 0, s->n * sizeof(uint32_t), st);
-        if (e == hipSuccess && mops) e = hipMemsetAsync(d_mops, 0, moff[s->n] * sizeof(float), st);
-        if (e != hipSuccess) { set_error("hipMemsetAsync failed: %s", hipGetErrorString(e)); return BAMM_ERR_HIP; }
-    }
-    for (size_t bi = 0; bi < s->buckets.size() && !rc; bi++) {
-        const Bucket& bk = s->buckets[bi];
-        ScoreKernelArgs a{};
-        a.sv = make_view(s, exc, bk.d_idx, bk.count, d_smask);
-        a.K = K; a.W = W; a.Y = Y; a.s = d_tab; a.mops = d_mops; a.mops_off = d_moff; a.zoops = d_zoops; a.z = d_z;
-        // beyond the length classes, or a log-odds table beyond the LDS of a CU (orders >= 6 at usual widths): the
-        // window-by-window scorer reads the table from global memory, same sums in the same order
-        if (bk.mclass == kLongClass || (size_t)W * Ys * sizeof(float) > 160u * 1024u) {
-            rc = launch_long_score(a, std::min(bk.count, (uint32_t)std::max(1, c->num_cus) * 8u), st);
-            continue;
-        }
-        const uint32_t threads = default_threads(c, bk.mclass);
-        uint32_t blocks = default_blocks(c, threads);
-        blocks = std::max(1u, std::min(blocks, (bk.count + threads / 64u - 1) / (threads / 64u)));
-        rc = launch_score(bk.mclass, a, blocks, threads, st);
-    }
+    DeviceScores d;
+    int rc = score_on_device(c, s, seq_mask, K, W, bg_order, v, vbg, mops != nullptr, false, tmp, &d);
     std::vector<uint32_t> hz(s->n);
     if (!rc) {
-        hipError_t e = ctx_download(c, zoops, d_zoops, s->n * sizeof(float)) ? hipErrorUnknown : hipSuccess;
-        if (e == hipSuccess && ctx_download(c, hz.data(), d_z, s->n * sizeof(uint32_t))) e = hipErrorUnknown;
-        if (e == hipSuccess && mops && ctx_download(c, mops, d_mops, moff[s->n] * sizeof(float))) e = hipErrorUnknown;
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        hipError_t e = ctx_download(c, zoops, d.zoops, s->n * sizeof(float)) ? hipErrorUnknown : hipSuccess;
+        if (e == hipSuccess && ctx_download(c, hz.data(), d.z, s->n * sizeof(uint32_t))) e = hipErrorUnknown;
+        if (e == hipSuccess && mops && ctx_download(c, mops, d.mops, d.moff[s->n] * sizeof(float))) e = hipErrorUnknown;
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
         if (e != hipSuccess) { set_error("bamm_logodds: copy failed: %s", hipGetErrorString(e)); rc = BAMM_ERR_HIP; }
     }
     if (!rc) for (uint64_t n = 0; n < s->n; n++) z[n] = hz[n];

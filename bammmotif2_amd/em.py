@@ -547,6 +547,41 @@ def logodds(ctx: Context, seqs: SeqSet, K: int, W: int, bg_order: int, v, vbg, w
     return (mops[:total] if want_mops else None), zoops[:N], z[:N]
 
 
+class Occurrences:
+    """What bamm_occurrences returns: per hit `seq`, `pos` (window start, 0-based), `score`, `fp`, `p`, `e`, and the scalars
+    of ScoreSeqSet::calcPvalues (`n_neg_scores`, `n_top`, `s_ntop`, `lambda_`) with the number of windows the device handed
+    to the host (`n_candidates`)."""
+
+    def __init__(self, seq, pos, score, fp, p, e, n_neg_scores, n_top, s_ntop, lambda_, n_candidates):
+        self.seq, self.pos, self.score, self.fp, self.p, self.e = seq, pos, score, fp, p, e
+        self.n_neg_scores, self.n_top, self.s_ntop, self.lambda_, self.n_candidates = n_neg_scores, n_top, s_ntop, lambda_, n_candidates
+
+    @property
+    def n_hits(self) -> int:
+        return len(self.p)
+
+
+def occurrences(ctx: Context, positives: SeqSet, negatives: SeqSet, K: int, W: int, bg_order: int, v, vbg,
+                p_cutoff: float) -> Occurrences:
+    """ScoreSeqSet::calcPvalues + the cut of ScoreSeqSet::write (ScoreSeqSet.cpp:70-126, :245-291) on the device: the windows
+    of `positives` with a p-value below `p_cutoff` against the scores of `negatives` (include/bamm_em.h: bamm_occurrences)."""
+    lib = ctx.lib
+    h = C.c_void_p()
+    check(lib.bamm_occurrences(ctx.h, positives.h, negatives.h, K, W, bg_order, _f32(v), _f32(vbg), p_cutoff, C.byref(h)))
+    try:
+        n_hits, n_neg, n_cand, n_top = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_uint32()
+        s_ntop, lam = C.c_float(), C.c_float()
+        check(lib.bamm_occ_info(h, C.byref(n_hits), C.byref(n_neg), C.byref(n_top), C.byref(s_ntop), C.byref(lam), C.byref(n_cand)))
+        n = n_hits.value
+        seq, fp = np.zeros(n, np.uint64), np.zeros(n, np.uint64)
+        pos = np.zeros(n, np.uint32)
+        score, p, e = np.zeros(n, np.float32), np.zeros(n, np.float32), np.zeros(n, np.float32)
+        check(lib.bamm_occ_get(h, *(a.ctypes.data_as(C.c_void_p) for a in (seq, pos, score, fp, p, e)), n))
+    finally:
+        lib.bamm_occ_destroy(h)
+    return Occurrences(seq, pos, score, fp, p, e, n_neg.value, n_top.value, np.float32(s_ntop.value), np.float32(lam.value), n_cand.value)
+
+
 def calculate_p(v, vbg, bg_order: int, K: int, W: int) -> np.ndarray:
     lib = abi.load()
     p = np.zeros(v_size(K, W), np.float32)

@@ -123,7 +123,8 @@ int logodds_zoops_write(const std::string& dir, const std::string& basename, con
                         const uint8_t* codes, const uint64_t* off, size_t n_seqs, bool revcomp, bool ss, uint32_t W,
                         const float* zoops, const uint64_t* z, std::string& err);
 
-// ScoreSeqSet::calcPvalues (seq_scoring/ScoreSeqSet.cpp:70-126): p-/e-values of every window
+// ScoreSeqSet::calcPvalues (seq_scoring/ScoreSeqSet.cpp:70-126): p-/e-values of every window; the formula itself is
+// csrc/occ_pvalue.h, shared with the device path (bamm_occurrences)
 void mops_pvalues(const float* pos_scores, size_t n_pos_scores, std::vector<float> neg_all, size_t posN,
                   std::vector<float>& p_out, std::vector<float>& e_out);
 
@@ -132,5 +133,9 @@ void mops_pvalues(const float* pos_scores, size_t n_pos_scores, std::vector<floa
 int occurrence_write(const std::string& dir, const std::string& basename, const std::vector<std::string>& headers,
                      const uint8_t* codes, const uint64_t* off, size_t n_seqs, bool ss, uint32_t W, const float* p,
                      const float* e, float cutoff, std::string& err);
+// the same file from the list of windows below the cut-off (bamm_occurrences: ascending sequence, then window start)
+int occurrence_write_hits(const std::string& dir, const std::string& basename, const std::vector<std::string>& headers,
+                          const uint8_t* codes, const uint64_t* off, size_t n_seqs, bool ss, uint32_t W, size_t n_hits,
+                          const uint64_t* seq, const uint32_t* pos, const float* p, const float* e, std::string& err);
 
 }  // namespace bammhost

@@ -17,6 +17,7 @@
 
 #include "bamm_host.h"
 #include "../csrc/glibc_rand.h"
+#include "../csrc/occ_pvalue.h"
 
 namespace bammhost {
 
@@ -625,41 +626,33 @@ int logodds_zoops_write(const std::string& dir, const std::string& basename, con
 void mops_pvalues(const float* pos_scores, size_t n_pos_scores, std::vector<float> neg, size_t posN,
                   std::vector<float>& p_out, std::vector<float>& e_out) {
     const size_t negN = neg.size();                    // ScoreSeqSet.cpp:75-93
-    const float eps = 1.0e-5;
     std::sort(neg.begin(), neg.end(), std::less<float>());
-    const size_t nTop = std::min(100, (int)negN / 10);
-    const float S_ntop = neg[nTop];
-    float lambda = 0.f;
-    for (size_t n = 0; n < nTop; n++) lambda += (neg[n] - S_ntop);
-    lambda = lambda / (float)nTop;
+    const bamm::OccScalars sc = bamm::occ_scalars(neg.data(), negN);
     p_out.resize(n_pos_scores);
     e_out.resize(n_pos_scores);
-    for (size_t i = 0; i < n_pos_scores; i++) {        // ScoreSeqSet.cpp:97-125
+    for (size_t i = 0; i < n_pos_scores; i++) {        // ScoreSeqSet.cpp:97-125: the branches are occ_window_pvalue's
         const float Sl = pos_scores[i];
         const size_t FPl = neg.end() - std::upper_bound(neg.begin(), neg.end(), Sl);
-        float p;
-        if (FPl == negN) {
-            p = 1.f;
-        } else if (FPl < 10 && fabs(lambda) > eps) {
-            p = float(nTop) / (float)negN * expf(-(Sl - S_ntop) / lambda);
-        } else {
-            const float SlHigher = neg[negN - FPl - 1], SlLower = neg[negN - FPl];
-            p = ((float)FPl + (SlHigher - Sl + eps) / (SlHigher - SlLower + eps)) / (float)negN;
-        }
+        float SlHigher = 0.f, SlLower = 0.f;
+        if (bamm::occ_uses_neighbours(FPl, sc)) { SlHigher = neg[negN - FPl - 1]; SlLower = neg[negN - FPl]; }
+        const float p = bamm::occ_window_pvalue(Sl, FPl, SlHigher, SlLower, sc);
         p_out[i] = p;
         e_out[i] = p * (float)posN;
     }
 }
 
-int occurrence_write(const std::string& dir, const std::string& basename, const std::vector<std::string>& headers,
-                     const uint8_t* codes, const uint64_t* off, size_t n_seqs, bool ss, uint32_t W, const float* p,
-                     const float* e, float cutoff, std::string& err) {
-    std::ofstream f(dir + '/' + basename + ".occurrence");
-    if (!f.is_open()) { err = "Error: Cannot write into output directory: " + dir; return 1; }
-    f << "seq\tlength\tstrand\tstart..end\tpattern\tp-value\te-value" << std::endl;
-    static const char B[] = "NACGT";
-    size_t o = 0;
-    for (size_t n = 0; n < n_seqs; n++) {
+namespace {
+
+// one row of ScoreSeqSet::write (ScoreSeqSet.cpp:262-288) for window i of sequence n
+struct OccurrenceRows {
+    std::ofstream f;
+    const std::vector<std::string>& headers;
+    const uint8_t* codes;
+    const uint64_t* off;
+    bool ss;
+    uint32_t W;
+    void row(size_t n, size_t i, float p, float e) {
+        static const char B[] = "NACGT";
         const size_t L0 = off[n + 1] - off[n], L = ss ? L0 : 2 * L0 + 1, seqlen = ss ? L : (L - 1) / 2;
         const uint8_t* c = codes + off[n];
         auto base_at = [&](size_t b) -> char {             // Sequence::getSequence(): forward, N, reverse complement
@@ -668,15 +661,43 @@ int occurrence_write(const std::string& dir, const std::string& basename, const 
             const uint8_t x = c[2 * L0 - b];
             return (x >= 1 && x <= 4) ? B[5 - x] : 'N';
         };
-        const size_t LW1 = L - W + 1;
-        for (size_t i = 0; i < LW1; i++) {
-            if (p[o + i] < cutoff) {
-                f << headers[n] << '\t' << seqlen << '\t' << ((i < seqlen) ? '+' : '-') << '\t' << i + 1 << ".." << i + W << '\t';
-                for (size_t m = i; m < i + W; m++) f << base_at(m);
-                f << '\t' << std::setprecision(3) << p[o + i] << '\t' << e[o + i] << std::endl;
-            }
-        }
+        f << headers[n] << '\t' << seqlen << '\t' << ((i < seqlen) ? '+' : '-') << '\t' << i + 1 << ".." << i + W << '\t';
+        for (size_t m = i; m < i + W; m++) f << base_at(m);
+        f << '\t' << std::setprecision(3) << p << '\t' << e << std::endl;
+    }
+    bool open(const std::string& dir, const std::string& basename, std::string& err) {
+        f.open(dir + '/' + basename + ".occurrence");
+        if (!f.is_open()) { err = "Error: Cannot write into output directory: " + dir; return false; }
+        f << "seq\tlength\tstrand\tstart..end\tpattern\tp-value\te-value" << std::endl;
+        return true;
+    }
+};
+
+}  // namespace
+
+int occurrence_write(const std::string& dir, const std::string& basename, const std::vector<std::string>& headers,
+                     const uint8_t* codes, const uint64_t* off, size_t n_seqs, bool ss, uint32_t W, const float* p,
+                     const float* e, float cutoff, std::string& err) {
+    OccurrenceRows rows{{}, headers, codes, off, ss, W};
+    if (!rows.open(dir, basename, err)) return 1;
+    size_t o = 0;
+    for (size_t n = 0; n < n_seqs; n++) {
+        const size_t L0 = off[n + 1] - off[n], L = ss ? L0 : 2 * L0 + 1, LW1 = L - W + 1;
+        for (size_t i = 0; i < LW1; i++)
+            if (p[o + i] < cutoff) rows.row(n, i, p[o + i], e[o + i]);
         o += LW1;
+    }
+    return 0;
+}
+
+int occurrence_write_hits(const std::string& dir, const std::string& basename, const std::vector<std::string>& headers,
+                          const uint8_t* codes, const uint64_t* off, size_t n_seqs, bool ss, uint32_t W, size_t n_hits,
+                          const uint64_t* seq, const uint32_t* pos, const float* p, const float* e, std::string& err) {
+    OccurrenceRows rows{{}, headers, codes, off, ss, W};
+    if (!rows.open(dir, basename, err)) return 1;
+    for (size_t h = 0; h < n_hits; h++) {
+        if (seq[h] >= n_seqs) { err = "Error: occurrence list names a sequence beyond the set"; return 1; }
+        rows.row((size_t)seq[h], pos[h], p[h], e[h]);
     }
     return 0;
 }

@@ -6,6 +6,7 @@
 
 #include <charconv>
 #include "bamm_host.h"
+#include "../csrc/occ_pvalue.h"
 
 using namespace bammhost;
 
@@ -131,6 +132,22 @@ void bh_auto_threads() { set_host_parallelism(0); }
 const char* bh_base_name(const char* path) {
     g_err = base_name(path);
     return g_err.c_str();
+}
+
+// the per-window formula the host and the device path share (csrc/occ_pvalue.h) on caller-provided ranks and neighbours
+int bh_occ_window_pvalues(const float* score, const uint64_t* fp, const float* higher, const float* lower, uint64_t n,
+                          const float* lowest, uint64_t negN, float* p_out, float* s_ntop, float* lambda, uint32_t* n_top) {
+    const bamm::OccScalars sc = bamm::occ_scalars(lowest, negN);
+    for (uint64_t i = 0; i < n; i++) p_out[i] = bamm::occ_window_pvalue(score[i], fp[i], higher[i], lower[i], sc);
+    *s_ntop = sc.S_ntop; *lambda = sc.lambda; *n_top = (uint32_t)sc.nTop;
+    return 0;
+}
+
+int bh_occurrence_hits(const char* dir, const char* base, const uint8_t* codes, const uint64_t* off, uint64_t n_seqs, int ss,
+                       uint32_t W, uint64_t n_hits, const uint64_t* seq, const uint32_t* pos, const float* p, const float* e) {
+    std::vector<std::string> headers;
+    for (uint64_t n = 0; n < n_seqs; n++) headers.push_back("seq" + std::to_string(n));
+    return occurrence_write_hits(dir, base, headers, codes, off, n_seqs, ss != 0, W, n_hits, seq, pos, p, e, g_err);
 }
 
 }  // extern "C"

@@ -65,6 +65,7 @@ void print_help() {
     printf("\t\t --timing (wall time per stage on stderr)   --hostSeeding (initFromPWM's pass on the host)\n");
     printf("\t\t --hostPacking (Sequence.cpp's encoding and the background counts on the host instead of the device)\n");
     printf("\t\t --hostSampler (SeqGenerator's negative sampler on the host instead of the device)\n");
+    printf("\t\t --hostPvalues (--scoreSeqset: ScoreSeqSet::calcPvalues on downloaded window scores instead of on the device)\n");
     printf("\t\t --gpus <INT> (1)   --deviceList <INT,INT,..>\n");
     printf("\t\t\t --EM: the sequences are sharded over the GPUs, one RCCL all-reduce of the count table per iteration;\n");
     printf("\t\t\t --FDR: cross-validation fold f runs on GPU f mod N (FDR.cpp:37 runs the folds on host threads).\n");
@@ -156,7 +157,7 @@ struct Options {                       // Global.cpp:6-96 defaults
     size_t cvFold = 4, mFold = 1, sOrder = 2, threads = 4;
     uint32_t max_iter = 1000;
     int device = 0;
-    bool timing = false, hostSeeding = false, hostPacking = false, hostSampler = false, forceComm = false, debug = false;
+    bool timing = false, hostSeeding = false, hostPacking = false, hostSampler = false, hostPvalues = false, forceComm = false, debug = false;
     size_t gpus = 1;                   // --gpus N: devices device .. device+N-1 (or --deviceList)
     std::vector<int> device_list;
 };
@@ -264,6 +265,7 @@ Options parse(int nargs, char** args) {
     o.hostSeeding = a.present(0, "hostSeeding");
     o.hostPacking = a.present(0, "hostPacking");
     o.hostSampler = a.present(0, "hostSampler");
+    o.hostPvalues = a.present(0, "hostPvalues");
     a.get(0, "gpus", o.gpus);
     {   // --deviceList 0,1,2: explicit devices (a device may appear twice for the fold replicas of --FDR; the
         // sharded --EM wants distinct ones, RCCL has one rank per GPU)
@@ -823,8 +825,13 @@ int main(int nargs, char* args[]) {
             if (!o.EM && o.seed_tag == "BaMM" && o.bg_file.empty()) die("No background Model file provided for initial search motif!");
             std::vector<float> neg_mops, neg_zoops, pos_mops, pos_zoops, pv, ev;
             std::vector<uint64_t> neg_z, pos_z;
-            if (score_set(devs[0].ctx, devs[0].neg, neg_len, sm, neg_mops, neg_zoops, nullptr, true, &neg_z)) die_abi("calcLogOdds");
-            if (score_set(devs[0].ctx, devs[0].full, kept_len, sm, pos_mops, pos_zoops, nullptr, true, &pos_z)) die_abi("calcLogOdds");
+            // --hostPvalues: every window's score comes to the host, which sorts, ranks and walks them; the default leaves
+            // them on the device (bamm_occurrences) and asks the scorer for the per-sequence maxima of --saveLogOdds only
+            const bool want_mops = o.hostPvalues;
+            if (want_mops || o.saveLogOdds) {
+                if (score_set(devs[0].ctx, devs[0].neg, neg_len, sm, neg_mops, neg_zoops, nullptr, want_mops, &neg_z)) die_abi("calcLogOdds");
+                if (score_set(devs[0].ctx, devs[0].full, kept_len, sm, pos_mops, pos_zoops, nullptr, want_mops, &pos_z)) die_abi("calcLogOdds");
+            }
             if (o.saveLogOdds) {                             // mainBaMM.cpp:204-208, :223-227
                 const std::vector<std::string> neg_headers(negN, "> bg_seq");                     // SeqGenerator.cpp:228
                 if (logodds_zoops_write(o.out_dir, o.basename + ".negSet", neg_headers, neg_codes.data(), neg_off.data(), negN, false,
@@ -832,9 +839,24 @@ int main(int nargs, char* args[]) {
                 if (logodds_zoops_write(o.out_dir, mbase, kept_headers, kept_codes.data(), kept_off.data(), kept_len.size(), !o.ss,
                                         o.ss, sm.W, pos_zoops.data(), pos_z.data(), err)) die(err);
             }
-            mops_pvalues(pos_mops.data(), pos_mops.size(), neg_mops, kept_len.size(), pv, ev);
-            if (occurrence_write(o.out_dir, mbase, kept_headers, kept_codes.data(), kept_off.data(), kept_len.size(), o.ss, sm.W,
-                                 pv.data(), ev.data(), o.pvalCutoff, err)) die(err);
+            if (o.hostPvalues) {
+                mops_pvalues(pos_mops.data(), pos_mops.size(), neg_mops, kept_len.size(), pv, ev);
+                if (occurrence_write(o.out_dir, mbase, kept_headers, kept_codes.data(), kept_off.data(), kept_len.size(), o.ss, sm.W,
+                                     pv.data(), ev.data(), o.pvalCutoff, err)) die(err);
+            } else {
+                bamm_occ* occ = nullptr;
+                if (bamm_occurrences(devs[0].ctx, devs[0].full, devs[0].neg, sm.K, sm.W, bg.K, sm.v.data(), bg.v.data(), o.pvalCutoff, &occ)) die_abi("calcPvalues");
+                uint64_t n_hits = 0;
+                bamm_occ_info(occ, &n_hits, nullptr, nullptr, nullptr, nullptr, nullptr);
+                std::vector<uint64_t> hit_seq(n_hits ? n_hits : 1);
+                std::vector<uint32_t> hit_pos(hit_seq.size());
+                pv.assign(hit_seq.size(), 0.f);
+                ev.assign(hit_seq.size(), 0.f);
+                if (bamm_occ_get(occ, hit_seq.data(), hit_pos.data(), nullptr, nullptr, pv.data(), ev.data(), hit_seq.size())) die_abi("calcPvalues");
+                bamm_occ_destroy(occ);
+                if (occurrence_write_hits(o.out_dir, mbase, kept_headers, kept_codes.data(), kept_off.data(), kept_len.size(), o.ss, sm.W,
+                                          n_hits, hit_seq.data(), hit_pos.data(), pv.data(), ev.data(), err)) die(err);
+            }
             stage("--scoreSeqset: score + p-values + .occurrence");
         }
     }

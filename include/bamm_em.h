@@ -356,6 +356,31 @@ int  bamm_logodds_subset(bamm_ctx* ctx, bamm_seqs* seqs, const uint8_t* seq_mask
                          uint32_t bg_order, const float* v_flat, const float* vbg, float* mops,
                          uint64_t mops_cap, float* zoops, uint64_t* z);
 
+/* ------------------------------------------------------------------ occurrences --------- */
+/* ScoreSeqSet::calcPvalues + the cut of ScoreSeqSet::write (ScoreSeqSet.cpp:70-126, :245-291): every window of the
+ * positives whose p-value is below p_cutoff, in ascending (sequence, window start) order.  Both sets are scored on the
+ * device, the negatives' scores are sorted there (ascending, as the reference sorts them) and every positive window is
+ * ranked against them there; what crosses to the host are the lowest nTop + 1 negative scores, a counter and the
+ * candidate windows -- those the device's own evaluation of the interpolation branch (:118-124) puts below the cut-off
+ * or leaves undecided (FPl < 10 with the exponential tail, :114-116: glibc's expf; a p that is not finite).  The host
+ * evaluates the reference's formula on the candidates with the code behind the CLI's --hostPvalues path, so p and e are
+ * that path's bits.  nTop = min(100, (int)negN / 10), S_ntop and lambda come from the LOWEST scores, as in the reference.
+ * One corner is undefined there and decided here: FPl = 0 with |lambda| <= 1e-5 reads one element past the sorted
+ * negatives (:120); this call takes +infinity for it (p = 0), the host path keeps reading what lies there.
+ * Errors: sets of another context, a sequence shorter than W, no negative window, more than 2^31 - 1 negative windows
+ * (the reference's (int)negN).  The result owns host arrays; bamm_occ_destroy releases it.                          */
+typedef struct bamm_occ bamm_occ;
+int  bamm_occurrences(bamm_ctx* ctx, bamm_seqs* positives, bamm_seqs* negatives, uint32_t K, uint32_t W,
+                      uint32_t bg_order, const float* v_flat, const float* vbg, float p_cutoff, bamm_occ** out);
+/* hits, negative windows, nTop, S_ntop, lambda, candidates the device handed over (>= hits); any pointer may be NULL */
+int  bamm_occ_info(const bamm_occ* occ, uint64_t* n_hits, uint64_t* n_neg_scores, uint32_t* n_top, float* s_ntop,
+                   float* lambda, uint64_t* n_candidates);
+/* per hit: sequence, window start i (0-based), log-odds score, FPl, p, e = p * (float)n_positives; any pointer may be
+ * NULL; cap = elements each array holds (>= n_hits)                                                              */
+int  bamm_occ_get(const bamm_occ* occ, uint64_t* seq, uint32_t* pos, float* score, uint64_t* fp, float* p, float* e,
+                  uint64_t cap);
+int  bamm_occ_destroy(bamm_occ* occ);
+
 /* Sequence::Sequence where the data will live: bamm_pack_codes_seeded + bamm_seqs_upload with the packing done on the
  * device (csrc/prep.hip) -- reverse complement, 2-bit stream, kmer_[i] next to unknown bases term by term with the
  * reference's rand() draws, the exception list.  The draws themselves are taken on the host (libc's one stream, entered
