@@ -15,8 +15,8 @@ import subprocess
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libbamm_em.so")
-SOURCES = ["model.hip", "kernels.hip", "grouped.hip", "grouped_long.hip", "grouped_xl.hip", "grouped_mix.hip", "grouped_mix1.hip", "mask.hip", "seed.hip", "long_seq.hip", "prep.hip", "negs.hip", "occ.hip", "ctx.cpp", "seqs.cpp", "plan.cpp", "em_pass.cpp", "em.cpp",
-           "score.cpp", "occurrences.cpp", "comm.cpp", "pack.cpp"]
+SOURCES = ["model.hip", "kernels.hip", "grouped.hip", "grouped_long.hip", "grouped_xl.hip", "grouped_mix.hip", "grouped_mix1.hip", "mask.hip", "seed.hip", "long_seq.hip", "prep.hip", "negs.hip", "occ.hip", "sites.hip", "ctx.cpp", "seqs.cpp", "plan.cpp", "em_pass.cpp", "em.cpp",
+           "score.cpp", "occurrences.cpp", "sites.cpp", "comm.cpp", "pack.cpp"]
 HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "device_utils.h"), os.path.join(CSRC, "grouped_kernel.h"), os.path.join(CSRC, "mixed_kernel.h"), os.path.join(CSRC, "update_kernel.h"), os.path.join(CSRC, "phase_clock.h"),
            os.path.join(HERE, "..", "include", "bamm_em.h")]
 # -Rpass-analysis=kernel-resource-usage: registers / scratch / spills of every kernel go to the compiler's
@@ -36,12 +36,19 @@ OBJDIR = os.path.join(HERE, "build")
 RESOURCES = os.path.join(OBJDIR, "resources.json")
 
 
+def _stem(src: str) -> str:
+    """Name of a source's object / remarks files: its own, or -- a host unit beside a kernel file of the same name
+    (sites.cpp, sites.hip) -- with `_host` behind it."""
+    stem, ext = os.path.splitext(src)
+    return stem + "_host" if ext == ".cpp" and stem + ".hip" in SOURCES else stem
+
+
 def _obj(src: str) -> str:
-    return os.path.join(OBJDIR, os.path.splitext(src)[0] + ".o")
+    return os.path.join(OBJDIR, _stem(src) + ".o")
 
 
 def _remarks(src: str) -> str:
-    return os.path.join(OBJDIR, os.path.splitext(src)[0] + ".remarks")
+    return os.path.join(OBJDIR, _stem(src) + ".remarks")
 
 
 def _diagnostics(text: str) -> str:
@@ -121,7 +128,7 @@ def _stale(target: str, deps) -> bool:
 # includes prep.h, is the private header of the C ABI's host units
 _HANDLES = [os.path.join(CSRC, "handles.h"), os.path.join(CSRC, "prep.h")]
 EXTRA_DEPS = {"prep.hip": [os.path.join(CSRC, "prep.h")], "negs.hip": [os.path.join(CSRC, "negs.h")],
-              "ctx.cpp": _HANDLES, "plan.cpp": _HANDLES, "em_pass.cpp": _HANDLES, "em.cpp": _HANDLES, "score.cpp": _HANDLES,
+              "ctx.cpp": _HANDLES, "plan.cpp": _HANDLES, "em_pass.cpp": _HANDLES, "em.cpp": _HANDLES, "score.cpp": _HANDLES, "sites.cpp": _HANDLES,
               "occurrences.cpp": _HANDLES + [os.path.join(CSRC, "occ_pvalue.h")],
               "seqs.cpp": _HANDLES + [os.path.join(CSRC, "negs.h"), os.path.join(CSRC, "glibc_rand.h")],
               "pack.cpp": [os.path.join(CSRC, "glibc_rand.h"), os.path.join(CSRC, "prep.h")]}

@@ -310,6 +310,35 @@ uint32_t occ_sort_blocks(uint32_t n, uint32_t num_cus);
 int launch_occ_sort(float* keys, uint32_t* alt, uint32_t* hist, uint32_t n, uint32_t blocks, hipStream_t st);
 int launch_occ_rank(const OccRankArgs& a, uint32_t blocks, hipStream_t st);
 
+// ---- sites (sites.hip; EM.cpp:577-601, GibbsSampling.cpp:105-116): dense r reduced to the windows at or above a cut-off ----
+struct SiteRec {                 // one site: sequence id in the resident set, window start, its r
+    uint32_t seq, pos;
+    float    r;
+};
+struct SitesArgs {
+    const float* r;              // dense r; sequence n starts at r[pos_off[n] - r_base]
+    uint64_t r_base;
+    uint32_t slot_layout;        // 0: reference layout, window i at L-W-i; 1: per position slot, window i at i+W-1 (e_slice)
+    const uint64_t* pos_off;     // [N+1] of the resident set
+    const uint32_t* len;         // [N]
+    uint32_t seq_begin, n_seqs;  // this launch: sequences seq_begin .. seq_begin + n_seqs - 1
+    uint32_t out_begin;          // the per-sequence outputs below are indexed by seq - out_begin (first sequence of the call)
+    uint32_t W;
+    float    cutoff;
+    uint32_t* count;             // sites per sequence (count pass: written; write pass: unused)
+    uint32_t* z;                 // 0 = no r above 0, else first arg-max window + 1
+    float*   r_best;
+    const unsigned long long* offset;   // write pass: the sequence's first record, counted from the call's first site
+    unsigned long long out_base; // write pass: sites of the call in front of `out`
+    SiteRec* out;
+    unsigned long long out_cap;  // records `out` holds
+};
+int launch_sites_count(const SitesArgs& a, uint32_t blocks, hipStream_t st);
+// offset[i] = base + count[0] + .. + count[i-1] for i < n; *total = base + the sum of all n
+int launch_sites_scan(const uint32_t* count, unsigned long long* offset, uint32_t n, unsigned long long base, unsigned long long* total,
+                      hipStream_t st);
+int launch_sites_write(const SitesArgs& a, uint32_t blocks, hipStream_t st);
+
 struct MaskSelect {              // device state of the radix select (EM.cpp:329-343)
     double   pos_count;          // number of windows (all ranks)
     double   rank;               // remaining 0-based rank in the descending order

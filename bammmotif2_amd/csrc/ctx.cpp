@@ -224,6 +224,7 @@ const TuningKey kTuningKeys[] = {
     {"peer_timeout_ms", &bamm_ctx::peer_timeout_ms, 1, 600000, 1, "1..600000"},
     {"scratch_cache_mb", &bamm_ctx::scratch_cap_bytes, 0, INT_MAX, 0, ">= 0"},
     {"list_threshold_pct", &bamm_ctx::list_threshold_pct, 0, 100, 0, "0..100"},
+    {"sites_chunk_positions", &bamm_ctx::sites_chunk_positions, 0, INT_MAX, 0, ">= 0"},
     {"group_size", &bamm_ctx::group_size, 2, 4, 0, "0 (auto) or 2..4"},
     {"group_layout", &bamm_ctx::group_layout, -1, 3, 8, "-1 (auto), 0..3 or 8 (mixed rows)"},
 };

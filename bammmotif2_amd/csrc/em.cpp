@@ -8,6 +8,50 @@
 
 using namespace bamm;
 
+// The dense r of sequences [begin,end) (a non-empty range), as the E pass the caller last ran gives it, on the device:
+// EM::mask's materialised r_, the sliced path's d_state after a replay of that pass (both span the whole set), or a
+// scratch block `tmp` owns that the fused / per-column / long-sequence kernels fill for the range.  The handle's pass
+// counters and event bookkeeping stay as they were.
+int bamm::dense_r_on_device(bamm_em* em, uint64_t begin, uint64_t end, DevTemps& tmp, DenseR* out) {
+    bamm_seqs* s = em->seqs;
+    hipStream_t st = em->ctx->stream;
+    const uint64_t base = s->h_pos_off[begin], total = s->h_pos_off[end] - base;
+    if (em->mask_done) {                                    // EM::mask keeps r_ materialised (EM.cpp:409-430)
+        *out = DenseR{em->d_mask_r, 0, false};
+        return BAMM_OK;
+    }
+    if (em->sliced) {
+        // the sliced E pass leaves r per position slot p (window start i = p-W+1) in d_state unless it is k_em_seq
+        uint8_t* saved_mask = em->d_mask;
+        em->d_mask = nullptr;                              // masked-out sequences still have an r
+        const uint32_t used = em->events_used, pass_no = em->pass_no;
+        int rc2 = run_accumulate(em, false, true, true);       // dense r
+        em->events_used = used; em->pass_no = pass_no;
+        em->d_mask = saved_mask;
+        if (rc2) return rc2;
+        *out = DenseR{em->d_state, 0, !em->e_fused};
+        return BAMM_OK;
+    }
+    float* d_r = nullptr;
+    int rc = tmp.scratch(&d_r, total);
+    if (rc) return rc;
+    if (hipMemsetAsync(d_r, 0, total * sizeof(float), st) != hipSuccess) { set_error("hipMemsetAsync failed"); return BAMM_ERR_HIP; }
+    for (size_t b = 0; b < em->ebuckets.size() && !rc; b++) {
+        const EmBucket& bk = em->ebuckets[b];
+        EmKernelArgs a{};
+        a.sv = make_view(s, em->exc, bk.d_idx, bk.count, nullptr);   // masked-out sequences still have an r in the reference
+        a.K = em->prm.K; a.W = em->prm.W; a.Y = em->Y;
+        a.s = em->s_last; a.q = em->q_last;                 // the E pass the caller last ran (EM.cpp:521)
+        a.acc = nullptr;                                    // responsibilities only
+        a.r_out = d_r; a.r_base = base; a.seq_begin = (uint32_t)begin; a.seq_end = (uint32_t)end;
+        a.fix_scale = 1.0f;
+        if (bk.mclass == kLongClass) { rc = launch_long_em(a, false, true, false, bk.blocks, st); continue; }
+        rc = launch_fused(em, bk, false, true, a, bucket_threads(em->ctx, bk), st);
+    }
+    *out = DenseR{d_r, base, false};
+    return rc;
+}
+
 extern "C" {
 
 // ------------------------------------------------------------------------------ EM ---------
@@ -568,51 +612,17 @@ int bamm_em_get_r(bamm_em* em, uint64_t begin, uint64_t end, float* out, uint64_
     if (total == 0) return BAMM_OK;
     BAMM_HIP(hipSetDevice(em->ctx->device));
     hipStream_t st = em->ctx->stream;
-    if (em->mask_done) {                                    // EM::mask keeps r_ materialised (EM.cpp:409-430)
-        if (int rc = ctx_download(em->ctx, out, em->d_mask_r + base, total * sizeof(float))) return rc;
-        BAMM_HIP(hipStreamSynchronize(st));
-        return BAMM_OK;
-    }
-    if (em->sliced) {
-        // the sliced E pass leaves r per position slot p (window start i = p-W+1) in d_state;
-        // the reference's index is L-W-i = L-1-p (EM.cpp:173)
-        uint8_t* saved_mask = em->d_mask;
-        em->d_mask = nullptr;                              // masked-out sequences still have an r
-        const uint32_t used = em->events_used, pass_no = em->pass_no;
-        int rc2 = run_accumulate(em, false, true, true);       // dense r, in the reference's layout
-        em->events_used = used; em->pass_no = pass_no;
-        em->d_mask = saved_mask;
-        if (rc2) return rc2;
-        if (int rc3 = ctx_download(em->ctx, out, em->d_state + base, total * sizeof(float))) return rc3;
-        BAMM_HIP(hipStreamSynchronize(st));
-        if (!em->e_fused)
-            for (uint64_t n = begin; n < end; n++) {
-                float* r = out + (s->h_pos_off[n] - base);
-                std::reverse(r, r + s->h_len[n]);
-            }
-        return BAMM_OK;
-    }
-    float* d_r = nullptr;
     DevTemps tmp(em->ctx);
-    int rc = tmp.scratch(&d_r, total);
+    DenseR dr;
+    int rc = dense_r_on_device(em, begin, end, tmp, &dr);
     if (rc) return rc;
-    if (hipMemsetAsync(d_r, 0, total * sizeof(float), st) != hipSuccess) { set_error("hipMemsetAsync failed"); return BAMM_ERR_HIP; }
-    for (size_t b = 0; b < em->ebuckets.size() && !rc; b++) {
-        const EmBucket& bk = em->ebuckets[b];
-        EmKernelArgs a{};
-        a.sv = make_view(s, em->exc, bk.d_idx, bk.count, nullptr);   // masked-out sequences still have an r in the reference
-        a.K = em->prm.K; a.W = em->prm.W; a.Y = em->Y;
-        a.s = em->s_last; a.q = em->q_last;                 // the E pass the caller last ran (EM.cpp:521)
-        a.acc = nullptr;                                    // responsibilities only
-        a.r_out = d_r; a.r_base = base; a.seq_begin = (uint32_t)begin; a.seq_end = (uint32_t)end;
-        a.fix_scale = 1.0f;
-        if (bk.mclass == kLongClass) { rc = launch_long_em(a, false, true, false, bk.blocks, st); continue; }
-        rc = launch_fused(em, bk, false, true, a, bucket_threads(em->ctx, bk), st);
-    }
-    if (!rc) {
-        rc = ctx_download(em->ctx, out, d_r, total * sizeof(float));
-        if (!rc && hipStreamSynchronize(st) != hipSuccess) { set_error("copy of r failed"); rc = BAMM_ERR_HIP; }
-    }
+    rc = ctx_download(em->ctx, out, dr.r + (base - dr.base), total * sizeof(float));
+    if (!rc && hipStreamSynchronize(st) != hipSuccess) { set_error("copy of r failed"); rc = BAMM_ERR_HIP; }
+    if (!rc && dr.slot_layout)                               // window start i sits at slot i+W-1; the reference's index is L-W-i (EM.cpp:173)
+        for (uint64_t n = begin; n < end; n++) {
+            float* r = out + (s->h_pos_off[n] - base);
+            std::reverse(r, r + s->h_len[n]);
+        }
     return rc;
 }
 
@@ -648,6 +658,16 @@ int bamm_em_plan_mixed(bamm_em* em, uint64_t* mixed_seqs) {
     uint64_t m = 0;
     for (auto& b : em->ebuckets) if (b.grouped && (b.layout & 8u)) m += b.count;
     *mixed_seqs = m;
+    return BAMM_OK;
+}
+
+int bamm_em_plan_paths(bamm_em* em, int* sliced, int* e_fused, uint64_t* long_seqs) {
+    if (!em) { set_error("null em"); return BAMM_ERR_ARG; }
+    uint64_t l = 0;
+    for (auto& b : em->ebuckets) if (b.mclass == kLongClass) l += b.count;
+    if (sliced) *sliced = em->sliced ? 1 : 0;
+    if (e_fused) *e_fused = em->sliced && em->e_fused ? 1 : 0;
+    if (long_seqs) *long_seqs = l;
     return BAMM_OK;
 }
 

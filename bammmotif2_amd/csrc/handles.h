@@ -1,6 +1,6 @@
 // The handles behind the C ABI (include/bamm_em.h) and the helpers their host units share: ctx.cpp (contexts, staging,
 // scratch pool), seqs.cpp (resident sequence sets), plan.cpp (launch plan of an EM handle), em_pass.cpp (one pass, one
-// update, the all-reduce), em.cpp (the EM entry points), score.cpp (the scorer) and occurrences.cpp (window p-values).  Host units only -- no kernel includes it.
+// update, the all-reduce), em.cpp (the EM entry points), score.cpp (the scorer), occurrences.cpp (window p-values) and sites.cpp (windows with r >= cut-off).  Host units only -- no kernel includes it.
 //
 // Reference seam these replace: class EM (/root/reference/src/refinement/EM.h:11-69,
 // EM.cpp:7-259,505-527) and ScoreSeqSet::calcLogOdds (seq_scoring/ScoreSeqSet.cpp:25-67).
@@ -99,6 +99,7 @@ struct bamm_ctx {
     std::unordered_map<void*, size_t> scratch_live;          // blocks handed out: bytes
     std::vector<std::pair<void*, size_t>> scratch_idle;      // blocks waiting for their next owner, oldest first
     size_t scratch_idle_bytes = 0, scratch_cap_bytes = 0;
+    uint32_t sites_chunk_positions = 0;                      // bamm_em_sites: dense r kept on the device at a time (0 = default)
     bool scratch_poison = false;                             // tests: every block is filled with 0xFF when it is handed out
     uint64_t scratch_hits = 0, scratch_misses = 0;
     // Every transfer of 64 KiB or more between the CALLER's memory and the device goes through this pinned area (two chunks,
@@ -344,6 +345,14 @@ struct Primers {
 bool plan_slices(bamm_em* em);
 // the launches of one pass, their blocks, the fused update and the sliced path's lists; primes each kernel it names
 int plan_launches(bamm_em* em, bool global_tables, const uint8_t* seq_mask, Primers& primers);
+
+// ---- em.cpp ----
+struct DenseR {
+    const float* r;              // sequence n of the set starts at r[pos_off[n] - base]
+    uint64_t base;
+    bool slot_layout;            // window start i at slot i+W-1 (the e_slice kernels) instead of the reference's L-W-i
+};
+int dense_r_on_device(bamm_em* em, uint64_t begin, uint64_t end, DevTemps& tmp, DenseR* out);
 
 // ---- em_pass.cpp ----
 int record_event(bamm_em* em, bool start);

@@ -378,6 +378,34 @@ class EM:
         check(self.lib.bamm_em_get_r(self.h, begin, end, out, total))
         return out[:total]
 
+    def sites_and_best(self, cutoff: float = 0.3, begin: int = 0, end: Optional[int] = None):
+        """One bamm_em_sites call over sequences [begin, end): ((seq, pos, r), (z, r_best, count)) -- what sites() and
+        best_sites() return, for a caller who wants both."""
+        end = self.seqs.n_seqs if end is None else end
+        h = C.c_void_p()
+        check(self.lib.bamm_em_sites(self.h, begin, end, cutoff, C.byref(h)))
+        try:
+            n_sites, n_seqs = C.c_uint64(), C.c_uint64()
+            check(self.lib.bamm_sites_info(h, C.byref(n_sites), C.byref(n_seqs)))
+            seq, pos, r = np.zeros(n_sites.value, np.uint64), np.zeros(n_sites.value, np.uint32), np.zeros(n_sites.value, np.float32)
+            z, r_best, count = np.zeros(n_seqs.value, np.uint32), np.zeros(n_seqs.value, np.float32), np.zeros(n_seqs.value, np.uint32)
+            check(self.lib.bamm_sites_get(h, *(a.ctypes.data_as(C.c_void_p) for a in (seq, pos, r)), n_sites.value))
+            check(self.lib.bamm_sites_best(h, *(a.ctypes.data_as(C.c_void_p) for a in (z, r_best, count)), n_seqs.value))
+        finally:
+            self.lib.bamm_sites_destroy(h)
+        return (seq, pos, r), (z, r_best, count)
+
+    def sites(self, cutoff: float = 0.3, begin: int = 0, end: Optional[int] = None):
+        """The windows of sequences [begin, end) with r >= cutoff -- r as getR() would report it now -- found on the device
+        (bamm_em_sites): `seq` (uint64, index in the handle's set), `pos` (uint32, window start, 0-based), `r` (float32), in
+        ascending (seq, pos) order.  cutoff = 0.3 gives the rows of EM::write's .positions (EM.cpp:577-601)."""
+        return self.sites_and_best(cutoff, begin, end)[0]
+
+    def best_sites(self, begin: int = 0, end: Optional[int] = None):
+        """Per sequence of [begin, end): `z` (0 = no window with r > 0, else the first arg-max window + 1, as
+        GibbsSampling.cpp:105-116 initialises it), `r_best` (its r) and `count` (windows with r >= 0.3)."""
+        return self.sites_and_best(0.3, begin, end)[1]
+
     # -- extensions -------------------------------------------------------------------------
     def iterate(self, n: int = 1):
         check(self.lib.bamm_em_iterate(self.h, n))
@@ -487,6 +515,13 @@ class EM:
         m = C.c_uint64()
         check(self.lib.bamm_em_plan_mixed(self.h, C.byref(m)))
         return int(m.value)
+
+    def plan_paths(self):
+        """(sliced, e_fused, long_seqs): the pass runs column slices; its E pass still holds the whole odds table; sequences
+        that go window by window (include/bamm_em.h: bamm_em_plan_paths)."""
+        sl, ef, ln = C.c_int(), C.c_int(), C.c_uint64()
+        check(self.lib.bamm_em_plan_paths(self.h, C.byref(sl), C.byref(ef), C.byref(ln)))
+        return bool(sl.value), bool(ef.value), int(ln.value)
 
     def close(self):
         if self.h:

@@ -82,6 +82,17 @@ int load_seeds(const std::string& path, const std::string& tag, uint32_t l_flank
 
 std::string base_name(const std::string& path);   // refinement/utils.h:66-85
 
+// EM::write's <basename>.positions (refinement/EM.cpp:577-601): one row per window whose r reaches the cut-off.
+// codes/off: FASTA codes of the forward strands; ss as on the command line.  r: per sequence L floats (L = the
+// forward length, or twice that + 1 with both strands) in the reference's layout, window start i at L-W-i ...
+int positions_write(const std::string& dir, const std::string& basename, const std::vector<std::string>& headers,
+                    const uint8_t* codes, const uint64_t* off, size_t n_seqs, bool ss, uint32_t W, const float* r, float cutoff,
+                    std::string& err);
+// ... or the list of those windows (bamm_em_sites: ascending sequence, then window start): the same file
+int positions_write_hits(const std::string& dir, const std::string& basename, const std::vector<std::string>& headers,
+                         const uint8_t* codes, const uint64_t* off, size_t n_seqs, bool ss, uint32_t W, size_t n_hits,
+                         const uint64_t* seq, const uint32_t* pos, std::string& err);
+
 }  // namespace bammhost
 
 // ======================= evaluation side: negatives, FDR statistics, occurrences ===================

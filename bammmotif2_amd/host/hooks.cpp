@@ -150,6 +150,19 @@ int bh_occurrence_hits(const char* dir, const char* base, const uint8_t* codes, 
     return occurrence_write_hits(dir, base, headers, codes, off, n_seqs, ss != 0, W, n_hits, seq, pos, p, e, g_err);
 }
 
+// EM::write's .positions from a site list / from dense r; headers: n_seqs C strings
+int bh_positions_hits(const char* dir, const char* base, const char* const* headers, const uint8_t* codes, const uint64_t* off,
+                      uint64_t n_seqs, int ss, uint32_t W, uint64_t n_hits, const uint64_t* seq, const uint32_t* pos) {
+    const std::vector<std::string> hd(headers, headers + n_seqs);
+    return positions_write_hits(dir, base, hd, codes, off, n_seqs, ss != 0, W, n_hits, seq, pos, g_err);
+}
+
+int bh_positions(const char* dir, const char* base, const char* const* headers, const uint8_t* codes, const uint64_t* off,
+                 uint64_t n_seqs, int ss, uint32_t W, const float* r, float cutoff) {
+    const std::vector<std::string> hd(headers, headers + n_seqs);
+    return positions_write(dir, base, hd, codes, off, n_seqs, ss != 0, W, r, cutoff, g_err);
+}
+
 }  // extern "C"
 
 // ---- evaluation-side hooks ---------------------------------------------------------------

@@ -542,4 +542,65 @@ int load_seeds(const std::string& path, const std::string& tag, uint32_t l_flank
     return 1;
 }
 
+// ---- EM::write's .positions (refinement/EM.cpp:577-601) ----
+namespace {
+
+// one row per window: header, the length shown (one strand's), strand, start..end (1-based), the window's bases
+struct PositionRows {
+    std::ofstream f;
+    const std::vector<std::string>& headers;
+    const uint8_t* codes;
+    const uint64_t* off;
+    bool ss;
+    uint32_t W;
+    bool open(const std::string& dir, const std::string& basename, std::string& err) {
+        f.open(dir + '/' + basename + ".positions");
+        if (!f.is_open()) { err = "Error: Cannot write into output directory: " + dir; return false; }
+        f << "seq\tlength\tstrand\tstart..end\tpattern\n";
+        return true;
+    }
+    size_t full_length(size_t n) const { const size_t L0 = off[n + 1] - off[n]; return ss ? L0 : 2 * L0 + 1; }
+    void row(size_t n, size_t i) {
+        static const char B[] = "NACGT";
+        const size_t L0 = off[n + 1] - off[n], shown = ss ? L0 : (full_length(n) - 1) / 2;
+        const uint8_t* c = codes + off[n];
+        f << headers[n] << '\t' << shown << '\t' << ((i < shown) ? '+' : '-') << '\t' << i + 1 << ".." << i + W << '\t';
+        for (size_t b = i; b < i + W; b++) {                 // Sequence::getSequence(): forward, N, reverse complement
+            if (b < L0) f << B[c[b] <= 4 ? c[b] : 0];
+            else if (ss || b == L0) f << 'N';
+            else { const uint8_t x = c[2 * L0 - b]; f << ((x >= 1 && x <= 4) ? B[5 - x] : 'N'); }
+        }
+        f << '\n';
+    }
+};
+
+}  // namespace
+
+int positions_write(const std::string& dir, const std::string& basename, const std::vector<std::string>& headers,
+                    const uint8_t* codes, const uint64_t* off, size_t n_seqs, bool ss, uint32_t W, const float* r, float cutoff,
+                    std::string& err) {
+    PositionRows rows{{}, headers, codes, off, ss, W};
+    if (!rows.open(dir, basename, err)) return 1;
+    size_t ro = 0;
+    for (size_t n = 0; n < n_seqs; n++) {
+        const size_t L = rows.full_length(n);
+        for (size_t i = 0; i + W <= L; i++)
+            if (r[ro + L - W - i] >= cutoff) rows.row(n, i);
+        ro += L;
+    }
+    return 0;
+}
+
+int positions_write_hits(const std::string& dir, const std::string& basename, const std::vector<std::string>& headers,
+                         const uint8_t* codes, const uint64_t* off, size_t n_seqs, bool ss, uint32_t W, size_t n_hits,
+                         const uint64_t* seq, const uint32_t* pos, std::string& err) {
+    PositionRows rows{{}, headers, codes, off, ss, W};
+    if (!rows.open(dir, basename, err)) return 1;
+    for (size_t h = 0; h < n_hits; h++) {
+        if (seq[h] >= n_seqs || (size_t)pos[h] + W > rows.full_length((size_t)seq[h])) { err = "Error: site list names a window beyond the set"; return 1; }
+        rows.row((size_t)seq[h], pos[h]);
+    }
+    return 0;
+}
+
 }  // namespace bammhost

@@ -66,6 +66,7 @@ void print_help() {
     printf("\t\t --hostPacking (Sequence.cpp's encoding and the background counts on the host instead of the device)\n");
     printf("\t\t --hostSampler (SeqGenerator's negative sampler on the host instead of the device)\n");
     printf("\t\t --hostPvalues (--scoreSeqset: ScoreSeqSet::calcPvalues on downloaded window scores instead of on the device)\n");
+    printf("\t\t --hostPositions (--saveBaMMs: .positions from downloaded responsibilities instead of the sites found on the device)\n");
     printf("\t\t --gpus <INT> (1)   --deviceList <INT,INT,..>\n");
     printf("\t\t\t --EM: the sequences are sharded over the GPUs, one RCCL all-reduce of the count table per iteration;\n");
     printf("\t\t\t --FDR: cross-validation fold f runs on GPU f mod N (FDR.cpp:37 runs the folds on host threads).\n");
@@ -157,7 +158,7 @@ struct Options {                       // Global.cpp:6-96 defaults
     size_t cvFold = 4, mFold = 1, sOrder = 2, threads = 4;
     uint32_t max_iter = 1000;
     int device = 0;
-    bool timing = false, hostSeeding = false, hostPacking = false, hostSampler = false, hostPvalues = false, forceComm = false, debug = false;
+    bool timing = false, hostSeeding = false, hostPacking = false, hostSampler = false, hostPvalues = false, hostPositions = false, forceComm = false, debug = false;
     size_t gpus = 1;                   // --gpus N: devices device .. device+N-1 (or --deviceList)
     std::vector<int> device_list;
 };
@@ -266,6 +267,7 @@ Options parse(int nargs, char** args) {
     o.hostPacking = a.present(0, "hostPacking");
     o.hostSampler = a.present(0, "hostSampler");
     o.hostPvalues = a.present(0, "hostPvalues");
+    o.hostPositions = a.present(0, "hostPositions");
     a.get(0, "gpus", o.gpus);
     {   // --deviceList 0,1,2: explicit devices (a device may appear twice for the fold replicas of --FDR; the
         // sharded --EM wants distinct ones, RCCL has one rank per GPU)
@@ -775,40 +777,45 @@ int main(int nargs, char* args[]) {
                     }
                     fn << std::endl;
                 }
-                // r of every kept sequence, shard after shard (the shards are consecutive ranges)
-                uint64_t total = 0;
-                for (uint32_t L : kept_len) total += L;
-                std::vector<float> r(total ? total : 1);
-                uint64_t ro_base = 0;
-                for (size_t d = 0; d < ndev; d++) {
-                    if (!ems[d]) continue;
-                    uint64_t ns = 0, tl = 0;
-                    bamm_seqs_info(devs[d].shard, &ns, &tl, nullptr, nullptr);
-                    if (tl && bamm_em_get_r(ems[d], 0, ns, r.data() + ro_base, tl)) die_abi("getR");
-                    ro_base += tl;
-                }
-                std::ofstream fp(o.out_dir + '/' + mbase + ".positions");
-                fp << "seq\tlength\tstrand\tstart..end\tpattern" << std::endl;
-                static const char B[] = "NACGT";
-                uint64_t ro = 0;
-                for (size_t s = 0; s < pos.size(); s++) {
-                    if (!keep[s]) continue;
-                    const size_t Lfull = packed->len[s], L0 = pos.off[s + 1] - pos.off[s];
-                    const size_t Lshown = o.ss ? Lfull : (Lfull - 1) / 2;
-                    for (size_t i = 0; i + motif.W <= Lfull; i++) {
-                        if (r[ro + Lfull - motif.W - i] >= 0.3f) {
-                            fp << pos.headers[s] << '\t' << Lshown << '\t' << ((i < Lshown) ? '+' : '-') << '\t' << i + 1 << ".." << i + motif.W << '\t';
-                            for (size_t b = i; b < i + motif.W; b++) {
-                                uint8_t code;                 // Sequence::getSequence(): forward, N, reverse complement
-                                if (b < L0) code = pos.codes[pos.off[s] + b];
-                                else if (o.ss || b == L0) code = 0;
-                                else { const uint8_t c = pos.codes[pos.off[s] + (2 * L0 - b)]; code = (c >= 1 && c <= 4) ? (uint8_t)(5 - c) : 0; }
-                                fp << B[code];
-                            }
-                            fp << std::endl;
-                        }
+                if (o.hostPositions) {
+                    // r of every kept sequence on the host, shard after shard (the shards are consecutive ranges), scanned there
+                    uint64_t total = 0;
+                    for (uint32_t L : kept_len) total += L;
+                    std::vector<float> r(total ? total : 1);
+                    uint64_t ro_base = 0;
+                    for (size_t d = 0; d < ndev; d++) {
+                        if (!ems[d]) continue;
+                        uint64_t ns = 0, tl = 0;
+                        bamm_seqs_info(devs[d].shard, &ns, &tl, nullptr, nullptr);
+                        if (tl && bamm_em_get_r(ems[d], 0, ns, r.data() + ro_base, tl)) die_abi("getR");
+                        ro_base += tl;
                     }
-                    ro += Lfull;
+                    if (positions_write(o.out_dir, mbase, kept_headers, kept_codes.data(), kept_off.data(), kept_len.size(), o.ss, motif.W,
+                                        r.data(), 0.3f, err)) die(err);
+                    if (timing) std::cerr << "[timing-beside] .positions: dense r, " << total * sizeof(float) << " bytes of r (computed: 4 per position)" << std::endl;
+                } else {
+                    // the windows with r >= 0.3 are found where r is (bamm_em_sites); a few rows per sequence cross
+                    std::vector<uint64_t> hit_seq;
+                    std::vector<uint32_t> hit_pos;
+                    uint64_t seq_base = 0;
+                    for (size_t d = 0; d < ndev; d++) {
+                        if (!ems[d]) continue;
+                        uint64_t ns = 0, n_sites = 0;
+                        bamm_seqs_info(devs[d].shard, &ns, nullptr, nullptr, nullptr);
+                        bamm_sites* sites = nullptr;
+                        if (bamm_em_sites(ems[d], 0, ns, 0.3f, &sites) || bamm_sites_info(sites, &n_sites, nullptr)) die_abi("sites");
+                        const size_t at = hit_seq.size();
+                        hit_seq.resize(at + n_sites);
+                        hit_pos.resize(at + n_sites);
+                        if (n_sites && bamm_sites_get(sites, hit_seq.data() + at, hit_pos.data() + at, nullptr, n_sites)) die_abi("sites");
+                        bamm_sites_destroy(sites);
+                        for (size_t h = at; h < hit_seq.size(); h++) hit_seq[h] += seq_base;
+                        seq_base += ns;
+                    }
+                    if (positions_write_hits(o.out_dir, mbase, kept_headers, kept_codes.data(), kept_off.data(), kept_len.size(), o.ss, motif.W,
+                                             hit_seq.size(), hit_seq.data(), hit_pos.data(), err)) die(err);
+                    if (timing) std::cerr << "[timing-beside] .positions: " << hit_seq.size() << " sites, " << hit_seq.size() * 12 + kept_len.size() * 12
+                                          << " bytes of records and per-sequence arrays (computed: 12 per site + 12 per sequence; the call also reads 8 bytes per chunk)" << std::endl;
                 }
             }
             std::cout << "optimized q = " << q << std::endl;   // mainBaMM.cpp:147

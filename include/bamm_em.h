@@ -22,6 +22,9 @@
  *       s       : [y][j], 4^(K+1) x W
  *       r       : per sequence L floats, reference's reversed index: r[L-W-i] <-> window
  *                 start i, slots >= L-W+1 are zero (EM.cpp:173,190-192)
+ *       sites   : the windows whose r reaches a cut-off, as (sequence, window start i, r) in ascending
+ *                 (sequence, i) order -- what EM::write lists in .positions (EM.cpp:577-601); found on
+ *                 the device, no window-sized array crosses to the host (bamm_em_sites)
  */
 #ifndef BAMM_EM_H_
 #define BAMM_EM_H_
@@ -141,6 +144,8 @@ int  bamm_ctx_set_launch(bamm_ctx* ctx, uint32_t blocks, uint32_t threads_per_bl
  *   "scratch_cache_mb" n  idle set-sized scratch blocks (dense r, lists, logs) a context keeps for its next handle
  *                       instead of freeing them (default: a quarter of the device's memory; 0 = keep nothing)
  *   "scratch_poison" 1/0 tests: fill every such block with 0xFF bytes when it is handed out (default 0)
+ *   "sites_chunk_positions" n  bamm_em_sites: positions of dense r the call keeps on the device at a time (whole
+ *                       sequences; 0 = the default, 2^27 positions = 512 MiB); read at the call, not at handle creation
  * There are no environment variables that change what the library computes or launches.          */
 int  bamm_ctx_set_tuning(bamm_ctx* ctx, const char* key, int value);
 
@@ -311,6 +316,26 @@ int  bamm_em_get_iteration(bamm_em* em, uint32_t* it);
 /* EM::getR() for sequences [begin,end): recomputed on demand from the s of the last EStep,
  * written in the reference's layout; out_off[n] = offset of sequence begin+n in `out`.       */
 int  bamm_em_get_r(bamm_em* em, uint64_t begin, uint64_t end, float* out, uint64_t out_cap);
+/* The windows of sequences [begin,end) with r >= cutoff -- r as bamm_em_get_r would report it at this moment, same
+ * preconditions, same errors -- and per sequence the best window.  What EM::write puts into .positions at 0.3
+ * (EM.cpp:577-601) and what GibbsSampling.cpp:105-116 initialises z from.  The dense r is produced on the device as
+ * for bamm_em_get_r (a range of a handle on the fused kernels: in chunks of whole sequences of at most
+ * "sites_chunk_positions" positions, a longer sequence alone) and reduced there (csrc/sites.hip): a count per
+ * sequence, a prefix sum, then every hit stored at its rank.  The order is ascending (sequence, window start) and
+ * does not depend on scheduling.  What crosses to the host: three words per sequence and 12 bytes per site.  NaN
+ * cutoff: BAMM_ERR_ARG.  cutoff <= 0 lists every window i <= L-W (never the zero slots behind).  begin == end: an
+ * empty result.  Sequences a seq_mask excludes still report, as in getR.  Pass counters and event bookkeeping of the
+ * handle stay as they were.  The result owns host arrays; bamm_sites_destroy releases it.                         */
+typedef struct bamm_sites bamm_sites;
+int  bamm_em_sites(bamm_em* em, uint64_t begin, uint64_t end, float cutoff, bamm_sites** out);
+int  bamm_sites_info(const bamm_sites* s, uint64_t* n_sites, uint64_t* n_seqs);
+/* per site, ascending (sequence, window start): sequence index in the handle's set, i (0-based), r; any pointer may
+ * be NULL; cap = elements each array holds (>= n_sites)                                                          */
+int  bamm_sites_get(const bamm_sites* s, uint64_t* seq, uint32_t* pos, float* r, uint64_t cap);
+/* per sequence of the range: z (0 = no window with r > 0, else the first arg-max window + 1) and its r (0 with z = 0);
+ * the number of its sites; any pointer may be NULL; cap >= n_seqs                                                */
+int  bamm_sites_best(const bamm_sites* s, uint32_t* z, float* r_best, uint32_t* count, uint64_t cap);
+int  bamm_sites_destroy(bamm_sites* s);
 /* per-iteration trace of optimize()/iterate(): what the reference prints with --verbose
  * (EM.cpp:112-115).  Returns up to cap entries, *n = entries available.                      */
 int  bamm_em_get_trace(bamm_em* em, float* llh, float* v_diff, float* q, uint32_t cap, uint32_t* n);
@@ -330,6 +355,11 @@ int  bamm_em_plan(bamm_em* em, uint64_t* grouped_seqs, uint64_t* percolumn_seqs,
 /* of the grouped ones: sequences that go through the mixed-row flavour (csrc/mixed_kernel.h: K = 2, the motif's
  * last W mod 3 groups of four columns on 6-mer rows)                                              */
 int  bamm_em_plan_mixed(bamm_em* em, uint64_t* mixed_seqs);
+/* which of the other paths the handle takes: *sliced = 1 when its tables exceed one CU's LDS and a pass runs column
+ * slices (k >= 4 at usual widths); *e_fused = 1 when the E pass of such a handle still holds the whole odds table (r in the
+ * reference's layout), 0 when it is sliced as well (r per position slot); *long_seqs = sequences beyond
+ * BAMM_MAX_SEQ_POSITIONS, which go window by window (long_seq.hip).  Any pointer may be NULL.               */
+int  bamm_em_plan_paths(bamm_em* em, int* sliced, int* e_fused, uint64_t* long_seqs);
 
 /* ------------------------------------------------------------------ seeding ------------- */
 /* The pass over the sequences of Motif::initFromPWM (Motif.cpp:228-311): 0th-order posterior of

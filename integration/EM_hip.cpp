@@ -236,7 +236,7 @@ void EM::printR() {                                      // EM.cpp:541-551
 }
 
 void EM::write(char* odir, std::string basename, bool ss) {   // EM.cpp:553-615: .counts and .positions
-    getR();
+    Device& d = dev(this);
     const std::string opath = std::string(odir) + '/' + basename;
     std::ofstream ofile_n((opath + ".counts").c_str());
     for (size_t j = 0; j < W_; j++) {
@@ -248,16 +248,21 @@ void EM::write(char* odir, std::string basename, bool ss) {   // EM.cpp:553-615:
     }
     std::ofstream ofile_pos((opath + ".positions").c_str());
     ofile_pos << "seq\tlength\tstrand\tstart..end\tpattern" << std::endl;
-    const float cutoff = 0.3f;
-    for (size_t n = 0; n < seqs_.size(); n++) {
+    // the windows with r >= 0.3 come from the device as a list, in the order of the reference's two loops
+    // (EM.cpp:585-601); r_ is not materialised for them
+    bamm_sites* sites = nullptr;
+    uint64_t n_sites = 0;
+    if (bamm_em_sites(d.em, 0, seqs_.size(), 0.3f, &sites) || bamm_sites_info(sites, &n_sites, nullptr)) die("sites");
+    std::vector<uint64_t> site_seq(n_sites ? n_sites : 1);
+    std::vector<uint32_t> site_pos(site_seq.size());
+    if (bamm_sites_get(sites, site_seq.data(), site_pos.data(), nullptr, site_seq.size())) die("sites");
+    bamm_sites_destroy(sites);
+    for (uint64_t h = 0; h < n_sites; h++) {
+        const size_t n = site_seq[h], i = site_pos[h];
         size_t L = seqs_[n]->getL();
         L = ss ? L : (L - 1) / 2;
-        for (size_t i = 0; i + W_ <= seqs_[n]->getL(); i++) {
-            if (r_[n][seqs_[n]->getL() - W_ - i] >= cutoff) {
-                ofile_pos << seqs_[n]->getHeader() << '\t' << L << '\t' << ((i < L) ? '+' : '-') << '\t' << i + 1 << ".." << i + W_ << '\t';
-                for (size_t b = i; b < i + W_; b++) ofile_pos << Alphabet::getBase(seqs_[n]->getSequence()[b]);
-                ofile_pos << std::endl;
-            }
-        }
+        ofile_pos << seqs_[n]->getHeader() << '\t' << L << '\t' << ((i < L) ? '+' : '-') << '\t' << i + 1 << ".." << i + W_ << '\t';
+        for (size_t b = i; b < i + W_; b++) ofile_pos << Alphabet::getBase(seqs_[n]->getSequence()[b]);
+        ofile_pos << std::endl;
     }
 }
