@@ -62,7 +62,8 @@ __device__ __forceinline__ void acc_add(long long* cell, long long v) {
 }
 // The sequence count shares its word with a count of blocks whose statistics were not finite (log Z of a Z = 0 at
 // q = 1, NaN odds from a degenerate model: the fp64 sums carry them, an integer cannot): bits 40.. of the word.  The
-// update turns a non-zero count back into NaN for llh, which is what the reference's float sum would hold.
+// update turns a non-zero count into NaN for llh: non-finite, as the reference's float sum would be there (-inf for the
+// log of a Z = 0, NaN for NaN odds; the two are not told apart).
 constexpr long long kStatBadUnit = 1ll << 40;
 // A sequence's log-likelihood and sum of responsibilities are rounded to the accumulator's units (2^-24, 2^-30) BEFORE
 // they are summed: fp64 sums of such values are exact (while below 2^29 / 2^23 per block: some 10^7 sequences), so a

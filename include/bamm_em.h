@@ -191,7 +191,12 @@ typedef struct bamm_em_params {
 void bamm_em_default_params(bamm_em_params* p);
 
 /* seq_mask: NULL, or n_seqs bytes (1 = sequence takes part).  vbg holds orders 0..bg_order.
- * Mirrors EM::EM (EM.cpp:7-43); v_init is Motif::getV() flattened.                           */
+ * Mirrors EM::EM (EM.cpp:7-43); v_init is Motif::getV() flattened.
+ * q, v_init, A and vbg are taken as they are, like the reference takes them.  Where they make a sequence's
+ * statistics non-finite (q = 1 with every window of a sequence on a zero of v: Z = 0; NaN or infinite odds), the
+ * pass still runs: the log-likelihood of that pass (bamm_em_get_llh, the trace) is NaN -- the reference's float
+ * sum would hold -inf or NaN there --, r of such a sequence is undefined and adds nothing to the counts, every other
+ * sequence is computed as usual, and nothing outlives the handle.                                              */
 int  bamm_em_create(bamm_ctx* ctx, bamm_seqs* seqs, const bamm_em_params* params,
                     const float* vbg, const float* A, const float* v_init,
                     const uint8_t* seq_mask, bamm_em** out);
