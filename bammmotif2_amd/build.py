@@ -15,8 +15,8 @@ import subprocess
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libbamm_em.so")
-SOURCES = ["model.hip", "kernels.hip", "grouped.hip", "grouped_long.hip", "grouped_xl.hip", "grouped_mix.hip", "grouped_mix1.hip", "mask.hip", "seed.hip", "long_seq.hip", "prep.hip", "negs.hip", "occ.hip", "sites.hip", "ctx.cpp", "seqs.cpp", "plan.cpp", "em_pass.cpp", "em.cpp",
-           "score.cpp", "occurrences.cpp", "sites.cpp", "comm.cpp", "pack.cpp"]
+SOURCES = ["model.hip", "kernels.hip", "grouped.hip", "grouped_long.hip", "grouped_xl.hip", "grouped_mix.hip", "grouped_mix1.hip", "mask.hip", "seed.hip", "long_seq.hip", "prep.hip", "negs.hip", "occ.hip", "sites.hip", "fdr.hip", "ctx.cpp", "seqs.cpp", "plan.cpp", "em_pass.cpp", "em.cpp",
+           "score.cpp", "occurrences.cpp", "sites.cpp", "fdr_stats.cpp", "comm.cpp", "pack.cpp"]
 HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "device_utils.h"), os.path.join(CSRC, "grouped_kernel.h"), os.path.join(CSRC, "mixed_kernel.h"), os.path.join(CSRC, "update_kernel.h"), os.path.join(CSRC, "phase_clock.h"),
            os.path.join(HERE, "..", "include", "bamm_em.h")]
 # -Rpass-analysis=kernel-resource-usage: registers / scratch / spills of every kernel go to the compiler's
@@ -31,7 +31,9 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=o
 # instructions, three times the instruction-cache misses (SQC_ICACHE_MISSES; profiles/r05_icache_alignment.txt) -- and every
 # unrelated change to the unit moves it.  Aligned, the placement is the same in every build (4 KB: 5.23 ms, 16 KB: 4.88, 64 KB: 4.90).
 # occ.hip restates a host fp32 expression bit for bit: IEEE division and kept fp32 denormals named explicitly (the compiler's defaults today)
-TU_FLAGS = {"occ.hip": ["-fhip-fp32-correctly-rounded-divide-sqrt", "-fno-gpu-flush-denormals-to-zero"], "grouped_long.hip": ["-falign-functions=16384"], "grouped_xl.hip": ["-falign-functions=16384"], "kernels.hip": ["-falign-functions=16384"]}
+# ... and so does fdr.hip (csrc/fdr_rows.h, shared with host/fdr.cpp)
+_IEEE = ["-fhip-fp32-correctly-rounded-divide-sqrt", "-fno-gpu-flush-denormals-to-zero"]
+TU_FLAGS = {"occ.hip": _IEEE, "fdr.hip": _IEEE, "grouped_long.hip": ["-falign-functions=16384"], "grouped_xl.hip": ["-falign-functions=16384"], "kernels.hip": ["-falign-functions=16384"]}
 OBJDIR = os.path.join(HERE, "build")
 RESOURCES = os.path.join(OBJDIR, "resources.json")
 
@@ -130,6 +132,7 @@ _HANDLES = [os.path.join(CSRC, "handles.h"), os.path.join(CSRC, "prep.h")]
 EXTRA_DEPS = {"prep.hip": [os.path.join(CSRC, "prep.h")], "negs.hip": [os.path.join(CSRC, "negs.h")],
               "ctx.cpp": _HANDLES, "plan.cpp": _HANDLES, "em_pass.cpp": _HANDLES, "em.cpp": _HANDLES, "score.cpp": _HANDLES, "sites.cpp": _HANDLES,
               "occurrences.cpp": _HANDLES + [os.path.join(CSRC, "occ_pvalue.h")],
+              "fdr.hip": [os.path.join(CSRC, "fdr_rows.h")], "fdr_stats.cpp": _HANDLES + [os.path.join(CSRC, "fdr_rows.h")],
               "seqs.cpp": _HANDLES + [os.path.join(CSRC, "negs.h"), os.path.join(CSRC, "glibc_rand.h")],
               "pack.cpp": [os.path.join(CSRC, "glibc_rand.h"), os.path.join(CSRC, "prep.h")]}
 FLAGS_STAMP = os.path.join(OBJDIR, "flags.txt")
@@ -224,7 +227,7 @@ HOST_SOURCES = ["io.cpp", "fdr.cpp", "hooks.cpp"]
 def build_host(force: bool = False, verbose: bool = False):
     """C++17 host code: libbamm_host.so (test hooks) and the `BaMMmotif` drop-in CLI."""
     build_library(force=False, verbose=verbose)
-    deps = [os.path.join(HOST, f) for f in HOST_SOURCES + ["main.cpp", "bamm_host.h"]] + [os.path.join(CSRC, "occ_pvalue.h"), LIB]
+    deps = [os.path.join(HOST, f) for f in HOST_SOURCES + ["main.cpp", "bamm_host.h"]] + [os.path.join(CSRC, "occ_pvalue.h"), os.path.join(CSRC, "fdr_rows.h"), LIB]
     outs = [HOST_LIB, CLI]
     if not force and all(os.path.exists(o) for o in outs) and \
             min(os.path.getmtime(o) for o in outs) >= max(os.path.getmtime(d) for d in deps):

@@ -310,6 +310,34 @@ uint32_t occ_sort_blocks(uint32_t n, uint32_t num_cus);
 int launch_occ_sort(float* keys, uint32_t* alt, uint32_t* hist, uint32_t n, uint32_t blocks, hipStream_t st);
 int launch_occ_rank(const OccRankArgs& a, uint32_t blocks, hipStream_t st);
 
+// ---- FDR --mops statistics on the device (fdr.hip; FDR.cpp:156-196, :278-333) ----
+// The walk over the two score lists is a merge: a block owns kFdrStepsPerBlock consecutive steps, a thread
+// kFdrStepsPerThread of them.
+constexpr uint32_t kFdrThreads = 256, kFdrStepsPerThread = 16, kFdrStepsPerBlock = kFdrThreads * kFdrStepsPerThread;
+struct FdrPeak {                 // what the peak kernels leave
+    float e_tp;                  // E_TP: the running maximum of tp after the last step (starts at 0)
+    uint32_t pad;
+    unsigned long long last_eq;  // 1 + the last step whose tp equals the running maximum in front of it; 0 = none
+};
+struct FdrWalkArgs {
+    const float* pos;            // ASCENDING scores (launch_occ_sort); the walk reads them from the top
+    const float* neg;
+    uint64_t n_pos, n_neg;
+    float    m_fold;             // fdr_mfold(posN, negN)
+    uint64_t n_blocks;           // ceil((n_pos + n_neg) / kFdrStepsPerBlock)
+    uint64_t* part;              // [n_blocks + 1] positives taken in front of each block's first step
+    float*   block_max;          // [n_blocks] max of tp over the block's steps, then (scan) the running maximum in front of the block
+    FdrPeak* peak;
+};
+int launch_fdr_peak(const FdrWalkArgs& a, hipStream_t st);   // partition, block maxima, scan, last equality
+// tp / fp / fdr / rec (any may be null) of steps [begin, end), written at [step - begin]; e_tp: FdrPeak::e_tp as the host read it
+int launch_fdr_rows(const FdrWalkArgs& a, uint64_t begin, uint64_t end, float e_tp, float* tp, float* fp, float* fdr, float* rec, hipStream_t st);
+// p[i - begin] for the ascending positives begin <= i < end
+int launch_fdr_pvalues(const float* pos, const float* neg, uint64_t n_neg, uint64_t begin, uint64_t end, float* p, hipStream_t st);
+// dst[seg[s].dst + k] = src[seg[s].src + k] for k < seg[s].len: the windows of one selected sequence out of a whole set's scores
+struct FdrSeg { unsigned long long src, dst; uint32_t len, pad; };
+int launch_fdr_gather(const float* src, float* dst, const FdrSeg* seg, uint32_t n_seg, uint32_t blocks, hipStream_t st);
+
 // ---- sites (sites.hip; EM.cpp:577-601, GibbsSampling.cpp:105-116): dense r reduced to the windows at or above a cut-off ----
 struct SiteRec {                 // one site: sequence id in the resident set, window start, its r
     uint32_t seq, pos;

@@ -258,6 +258,19 @@ struct bamm_em {
     bamm::EmBook books[4] = {};                 // snapshot right after update i at [i & 3]
 };
 
+// --FDR --mops statistics (fdr_stats.cpp): the window scores of every fold, positives and negatives, in two device arrays
+// from the context's scratch pool that grow geometrically (a fold's count is not known before it is scored); sorted in
+// place by bamm_fdr_statistics, which also leaves the walk's partition and the peak.
+struct bamm_fdr {
+    bamm_ctx* ctx = nullptr;
+    float* d[2] = {nullptr, nullptr};           // [0] positives, [1] negatives
+    uint64_t n[2] = {0, 0}, cap[2] = {0, 0};
+    bool done = false, with_pvalues = false;    // statistics ran: no more scores
+    uint64_t posN = 0, negN = 0, n_rows = 0;
+    float e_tp = 0.0f;
+    bamm::FdrWalkArgs walk{};                   // part / block_max / peak: owned, freed with the handle
+};
+
 namespace bamm {
 
 // ---- ctx.cpp ----

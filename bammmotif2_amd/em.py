@@ -617,6 +617,70 @@ def occurrences(ctx: Context, positives: SeqSet, negatives: SeqSet, K: int, W: i
     return Occurrences(seq, pos, score, fp, p, e, n_neg.value, n_top.value, np.float32(s_ntop.value), np.float32(lam.value), n_cand.value)
 
 
+def fdr_geometry():
+    """(steps per thread, steps per block) of the ranking walk's kernels in this build (csrc/fdr.hip)."""
+    spt, spb = C.c_uint32(), C.c_uint32()
+    check(abi.load().bamm_fdr_geometry(C.byref(spt), C.byref(spb)))
+    return spt.value, spb.value
+
+
+class FdrMops:
+    """FDR::calculatePR's MOPS branch and FDR::calculatePvalues over window scores kept on the device
+    (include/bamm_em.h: bamm_fdr).  Add the folds' scores, call statistics() once, then fetch rows / p-values by range."""
+
+    def __init__(self, ctx: Context):
+        self.ctx, self.lib = ctx, ctx.lib
+        self.h = C.c_void_p()
+        check(self.lib.bamm_fdr_create(ctx.h, C.byref(self.h)))
+
+    def add_set(self, negative: bool, seqs: SeqSet, K: int, W: int, bg_order: int, v, vbg, mask=None):
+        mk = None
+        if mask is not None:
+            mk = np.ascontiguousarray(mask, np.uint8)
+            assert len(mk) == seqs.n_seqs
+        check(self.lib.bamm_fdr_add_set(self.h, 1 if negative else 0, seqs.h, None if mk is None else mk.ctypes.data_as(C.c_void_p),
+                                        K, W, bg_order, _f32(v), _f32(vbg)))
+
+    def add_scores(self, negative: bool, scores):
+        a = np.ascontiguousarray(scores, np.float32)
+        check(self.lib.bamm_fdr_add_scores(self.h, 1 if negative else 0, a.ctypes.data_as(C.c_void_p), a.size))
+
+    def statistics(self, posN: int, negN: int, with_pvalues: bool = True):
+        check(self.lib.bamm_fdr_statistics(self.h, posN, negN, 1 if with_pvalues else 0))
+
+    def info(self) -> dict:
+        n_pos, n_neg, n_rows, e_tp, occ = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_float(), C.c_float()
+        check(self.lib.bamm_fdr_info(self.h, C.byref(n_pos), C.byref(n_neg), C.byref(n_rows), C.byref(e_tp), C.byref(occ)))
+        return dict(n_pos=n_pos.value, n_neg=n_neg.value, n_rows=n_rows.value, e_tp=np.float32(e_tp.value), occ_mult=np.float32(occ.value))
+
+    def rows(self, begin: int = 0, end: Optional[int] = None, columns=("tp", "fp", "fdr", "rec")) -> dict:
+        """The named columns of rows [begin, end) (end None: n_rows)."""
+        if end is None:
+            end = self.info()["n_rows"]
+        out = {k: np.zeros(max(end - begin, 0), np.float32) for k in columns}
+        ptrs = [out[k].ctypes.data_as(C.c_void_p) if k in out else None for k in ("tp", "fp", "fdr", "rec")]
+        check(self.lib.bamm_fdr_rows(self.h, begin, end, *ptrs))
+        return out
+
+    def pvalues(self, begin: int = 0, end: Optional[int] = None) -> np.ndarray:
+        if end is None:
+            end = self.info()["n_pos"]
+        p = np.zeros(max(end - begin, 0), np.float32)
+        check(self.lib.bamm_fdr_pvalues(self.h, begin, end, p.ctypes.data_as(C.c_void_p)))
+        return p
+
+    def close(self):
+        if self.h:
+            self.lib.bamm_fdr_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def calculate_p(v, vbg, bg_order: int, K: int, W: int) -> np.ndarray:
     lib = abi.load()
     p = np.zeros(v_size(K, W), np.float32)

@@ -4,6 +4,7 @@
 // each function (paths relative to /root/reference/src); the code is written from scratch.
 #pragma once
 #include <cstdint>
+#include <functional>
 #include <string>
 #include <vector>
 
@@ -124,6 +125,13 @@ void fdr_statistics(std::vector<float> pos_max, std::vector<float> neg_max, std:
                     bool with_pvalues, FdrResult& out);
 int fdr_write(const std::string& dir, const std::string& basename, const FdrResult& r, size_t posN, size_t negN,
               bool mops, bool zoops, bool save_prs, bool save_pvalues, std::string& err);   // FDR.cpp:338-410
+
+// the MOPS files of fdr_write from rows fetched range by range [begin, end) -- the device path (bamm_fdr_rows,
+// bamm_fdr_pvalues): the same bytes, host memory for one chunk of rows.  A fetch returns non-zero with `err` set.
+using FdrRowFetch = std::function<int(uint64_t begin, uint64_t end, float* tp, float* fp, float* fdr, float* rec, std::string& err)>;
+using FdrPvalueFetch = std::function<int(uint64_t begin, uint64_t end, float* p, std::string& err)>;
+int fdr_write_mops_chunked(const std::string& dir, const std::string& basename, float occ_mult, uint64_t n_rows, const FdrRowFetch& rows,
+                           uint64_t n_pvalues, const FdrPvalueFetch& pvalues, bool save_prs, bool save_pvalues, std::string& err);
 
 // --saveLogOdds: FDR::write's .zoops.logOdds / .mops.logOdds (FDR.cpp:416-450) and
 // ScoreSeqSet::writeLogOdds' .logOddsZoops (ScoreSeqSet.cpp:293-331)

@@ -18,6 +18,7 @@
 #include "bamm_host.h"
 #include "../csrc/glibc_rand.h"
 #include "../csrc/occ_pvalue.h"
+#include "../csrc/fdr_rows.h"
 
 namespace bammhost {
 
@@ -322,9 +323,9 @@ void fdr_statistics(std::vector<float> posMax, std::vector<float> negMax, std::v
                     std::vector<float> negAll, size_t posN, size_t negN, float q, bool mops, bool zoops,
                     bool with_pvalues, FdrResult& r) {
     r = FdrResult();
-    const float mFold = (float)negN / (float)posN;
+    const float mFold = bamm::fdr_mfold(posN, negN);
     srand(42);                                         // FDR.cpp:153
-    if (mops) {                                        // FDR.cpp:156-196
+    if (mops) {                                        // FDR.cpp:156-196; the numbers are csrc/fdr_rows.h's, as on the device (csrc/fdr.hip)
         sort_scores(posAll, true);
         sort_scores(negAll, true);
         size_t ip = 0, in = 0;
@@ -336,14 +337,15 @@ void fdr_statistics(std::vector<float> posMax, std::vector<float> negMax, std::v
             // list is treated as "-inf" instead of reading stale heap memory
             const bool take_pos = (ip < posAll.size()) && (in >= negAll.size() || posAll[ip] > negAll[in]);
             if (take_pos) ip++; else in++;
-            r.mops_tp.push_back((float)ip - (float)in / mFold);
-            r.mops_fp.push_back((float)in / mFold);
-            if (E_TP == r.mops_tp[i]) idx_max = i;
-            if (E_TP < r.mops_tp[i]) E_TP = r.mops_tp[i];
+            r.mops_tp.push_back(bamm::fdr_tp(ip, in, mFold));
+            r.mops_fp.push_back(bamm::fdr_fp(in, mFold));
+            const bamm::FdrPeakStep step = bamm::fdr_peak_step(E_TP, r.mops_tp[i]);
+            if (step.equal) idx_max = i;
+            E_TP = step.e_tp;
         }
         for (size_t i = 0; i < idx_max && i < len_all; i++) {
-            r.mops_fdr.push_back(r.mops_fp[i] / (r.mops_tp[i] + r.mops_fp[i]));
-            r.mops_rec.push_back(r.mops_tp[i] / E_TP);
+            r.mops_fdr.push_back(bamm::fdr_fdr(r.mops_tp[i], r.mops_fp[i]));
+            r.mops_rec.push_back(bamm::fdr_rec(r.mops_tp[i], E_TP));
         }
         r.occ_mult = E_TP / (float)posN;
     }
@@ -422,10 +424,7 @@ void fdr_statistics(std::vector<float> posMax, std::vector<float> negMax, std::v
             for (size_t i = 0; i < pos.size(); i++) {
                 const size_t low = std::lower_bound(neg.begin(), neg.end(), pos[i]) - neg.begin();
                 const size_t up = std::upper_bound(neg.begin(), neg.end(), pos[i]) - neg.begin();
-                float p = 1.0f - (float)(up + low) / (2.0f * (float)neg.size());
-                if (p < 1.e-6) p = 1.e-6;
-                if (p > 1.0f) p = 1.0f;
-                out.push_back(p);
+                out.push_back(bamm::fdr_pvalue(low, up, neg.size()));
             }
         };
         if (mops) pv(posAll, negAll, r.mops_pvalue);
@@ -560,6 +559,39 @@ int fdr_write(const std::string& dir, const std::string& basename, const FdrResu
         if (mops) {
             std::ofstream f(opath + ".mops.pvalues");
             write_rows(f, r.mops_pvalue.size(), 3, [&](RowWriter& w, size_t i) { w.num(r.mops_pvalue[i]); w.nl(); });
+        }
+    }
+    return 0;
+}
+
+// .mops.stats / .mops.pvalues of fdr_write from rows that are fetched range by range (bamm_fdr_rows / bamm_fdr_pvalues):
+// the same bytes, with a few million rows on the host at a time instead of every window's
+int fdr_write_mops_chunked(const std::string& dir, const std::string& basename, float occ_mult, uint64_t n_rows, const FdrRowFetch& rows,
+                           uint64_t n_pvalues, const FdrPvalueFetch& pvalues, bool save_prs, bool save_pvalues, std::string& err) {
+    constexpr uint64_t kChunk = uint64_t(1) << 22;
+    const std::string opath = dir + '/' + basename;
+    std::vector<float> col[4];
+    if (save_prs) {
+        std::ofstream f(opath + ".mops.stats");
+        if (!f.is_open()) { err = "Error: Cannot write into output directory: " + dir; return 1; }
+        f << "TP" << '\t' << "FP" << '\t' << "FDR" << '\t' << "Recall" << '\t' << occ_mult << std::endl;
+        for (auto& c : col) c.resize((size_t)std::min(kChunk, n_rows));
+        for (uint64_t at = 0; at < n_rows; at += kChunk) {
+            const uint64_t stop = std::min(n_rows, at + kChunk);
+            if (rows(at, stop, col[0].data(), col[1].data(), col[2].data(), col[3].data(), err)) return 1;
+            write_rows(f, (size_t)(stop - at), 6, [&](RowWriter& w, size_t i) {
+                w.num(col[0][i]); w.tab(); w.num(col[1][i]); w.tab(); w.num(col[2][i]); w.tab(); w.num(col[3][i]); w.tab(); w.nl();
+            });
+        }
+    }
+    if (save_pvalues) {
+        std::ofstream f(opath + ".mops.pvalues");
+        if (!f.is_open()) { err = "Error: Cannot write into output directory: " + dir; return 1; }
+        col[0].resize((size_t)std::min(kChunk, n_pvalues));
+        for (uint64_t at = 0; at < n_pvalues; at += kChunk) {
+            const uint64_t stop = std::min(n_pvalues, at + kChunk);
+            if (pvalues(at, stop, col[0].data(), err)) return 1;
+            write_rows(f, (size_t)(stop - at), 3, [&](RowWriter& w, size_t i) { w.num(col[0][i]); w.nl(); });
         }
     }
     return 0;

@@ -205,6 +205,20 @@ int bh_fdr_stats(const float* pos_max, uint64_t n_pos_max, const float* neg_max,
     return fdr_write(dir, base, r, posN, negN, mops != 0, zoops != 0, true, save_pvalues != 0, g_err);
 }
 
+// the MOPS half of fdr_statistics as arrays: tp / fp (n_pos + n_neg values), fdr / rec (*n_rows values; room for n_pos + n_neg),
+// the p-values of the ascending positives (n_pos values); any array may be NULL
+int bh_fdr_mops_rows(const float* pos_all, uint64_t n_pos, const float* neg_all, uint64_t n_neg, uint64_t posN, uint64_t negN,
+                     uint64_t* n_rows, float* occ_mult, float* tp, float* fp, float* fdr, float* rec, float* pvalues) {
+    FdrResult r;
+    fdr_statistics({}, {}, std::vector<float>(pos_all, pos_all + n_pos), std::vector<float>(neg_all, neg_all + n_neg), posN, negN, 0.f,
+                   true, false, pvalues != nullptr, r);
+    auto out = [](float* dst, const std::vector<float>& v) { if (dst && !v.empty()) memcpy(dst, v.data(), v.size() * sizeof(float)); };
+    if (n_rows) *n_rows = r.mops_fdr.size();
+    if (occ_mult) *occ_mult = r.occ_mult;
+    out(tp, r.mops_tp); out(fp, r.mops_fp); out(fdr, r.mops_fdr); out(rec, r.mops_rec); out(pvalues, r.mops_pvalue);
+    return 0;
+}
+
 // tests: format_g against std::to_chars (which is printf's %g) on n floats; returns the number of differing strings and
 // the first offender's bits
 uint64_t bh_format_g_check(const float* x, uint64_t n, int precision, uint32_t* first_bad_bits) {

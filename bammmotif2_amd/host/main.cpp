@@ -67,6 +67,7 @@ void print_help() {
     printf("\t\t --hostSampler (SeqGenerator's negative sampler on the host instead of the device)\n");
     printf("\t\t --hostPvalues (--scoreSeqset: ScoreSeqSet::calcPvalues on downloaded window scores instead of on the device)\n");
     printf("\t\t --hostPositions (--saveBaMMs: .positions from downloaded responsibilities instead of the sites found on the device)\n");
+    printf("\t\t --hostFdr (--FDR --mops: the MOPS statistics from downloaded window scores instead of on the device)\n");
     printf("\t\t --gpus <INT> (1)   --deviceList <INT,INT,..>\n");
     printf("\t\t\t --EM: the sequences are sharded over the GPUs, one RCCL all-reduce of the count table per iteration;\n");
     printf("\t\t\t --FDR: cross-validation fold f runs on GPU f mod N (FDR.cpp:37 runs the folds on host threads).\n");
@@ -158,7 +159,7 @@ struct Options {                       // Global.cpp:6-96 defaults
     size_t cvFold = 4, mFold = 1, sOrder = 2, threads = 4;
     uint32_t max_iter = 1000;
     int device = 0;
-    bool timing = false, hostSeeding = false, hostPacking = false, hostSampler = false, hostPvalues = false, hostPositions = false, forceComm = false, debug = false;
+    bool timing = false, hostSeeding = false, hostPacking = false, hostSampler = false, hostPvalues = false, hostPositions = false, hostFdr = false, forceComm = false, debug = false;
     size_t gpus = 1;                   // --gpus N: devices device .. device+N-1 (or --deviceList)
     std::vector<int> device_list;
 };
@@ -268,6 +269,7 @@ Options parse(int nargs, char** args) {
     o.hostSampler = a.present(0, "hostSampler");
     o.hostPvalues = a.present(0, "hostPvalues");
     o.hostPositions = a.present(0, "hostPositions");
+    o.hostFdr = a.present(0, "hostFdr");
     a.get(0, "gpus", o.gpus);
     {   // --deviceList 0,1,2: explicit devices (a device may appear twice for the fold replicas of --FDR; the
         // sharded --EM wants distinct ones, RCCL has one rank per GPU)
@@ -641,11 +643,19 @@ int main(int nargs, char* args[]) {
     // are merged in fold order afterwards, so the files do not depend on the plan or on which fold finishes first.
     struct FoldOut { std::vector<float> posMax, negMax, posAll, negAll; float q = 0.f; std::string log, err; };
     std::vector<std::vector<FoldOut>> fold_results(seeds.motifs.size());
+    // --mops: the window scores of every fold stay where they are scored and the MOPS statistics are computed there
+    // (bamm_fdr, one handle per motif) when all folds run on ONE context; a plan over several contexts, --saveLogOdds
+    // (which prints the scores) and --hostFdr download them and take host/fdr.cpp's path
+    const bool device_fdr = need_gpu && o.FDR && o.mops && !o.hostFdr && !o.saveLogOdds &&
+                            std::all_of(fold_slot.begin(), fold_slot.end(), [&](size_t s) { return s == fold_slot[0]; });
+    std::vector<bamm_fdr*> fdr_handles(seeds.motifs.size(), nullptr);
     auto run_folds = [&](size_t n, std::vector<FoldOut>& folds) {
         const size_t cv = o.cvFold, P = kept_len.size();
         const Motif& seed = seeds.motifs[n];
         folds.assign(cv, FoldOut());
         for (auto& f : folds) f.q = seed.q;
+        if (device_fdr && bamm_fdr_create(devs[fold_slot[0]].ctx, &fdr_handles[n])) { folds[0].err = bamm_last_error(); return; }
+        bamm_fdr* const fdr = fdr_handles[n];
         std::vector<size_t> slots_in_use;
         for (size_t f = 0; f < cv; f++)
             if (std::find(slots_in_use.begin(), slots_in_use.end(), fold_slot[f]) == slots_in_use.end()) slots_in_use.push_back(fold_slot[f]);
@@ -674,19 +684,22 @@ int main(int nargs, char* args[]) {
                 fo.log = os.str();
             }
             std::vector<float> mops, zoops;
-            if (score_set(dv.ctx, dv.full, kept_len, m, mops, zoops, test.data(), o.mops)) { fo.err = bamm_last_error(); return; }
+            const bool host_mops = o.mops && !fdr;
+            if (score_set(dv.ctx, dv.full, kept_len, m, mops, zoops, test.data(), host_mops)) { fo.err = bamm_last_error(); return; }
+            if (fdr && bamm_fdr_add_set(fdr, 0, dv.full, test.data(), m.K, m.W, bg.K, m.v.data(), bg.v.data())) { fo.err = bamm_last_error(); return; }
             size_t o_m = 0;
             for (size_t i = 0; i < P; i++) {
                 const size_t nw = kept_len[i] - m.W + 1;
                 if (test[i]) {
-                    if (o.mops) fo.posAll.insert(fo.posAll.end(), mops.begin() + o_m, mops.begin() + o_m + nw);
+                    if (host_mops) fo.posAll.insert(fo.posAll.end(), mops.begin() + o_m, mops.begin() + o_m + nw);
                     if (o.zoops) fo.posMax.push_back(zoops[i]);
                 }
                 o_m += nw;
             }
             // negSet = every cv-th negative (FDR.cpp:58-60): resident as a set of its own, scored as a whole
-            if (score_set(dv.ctx, dv.neg_cv, neg_cv_len, m, mops, zoops, nullptr, o.mops)) { fo.err = bamm_last_error(); return; }
-            if (o.mops) fo.negAll = mops;
+            if (score_set(dv.ctx, dv.neg_cv, neg_cv_len, m, mops, zoops, nullptr, host_mops)) { fo.err = bamm_last_error(); return; }
+            if (fdr && bamm_fdr_add_set(fdr, 1, dv.neg_cv, nullptr, m.K, m.W, bg.K, m.v.data(), bg.v.data())) { fo.err = bamm_last_error(); return; }
+            if (host_mops) fo.negAll = mops;
             if (o.zoops) fo.negMax = zoops;
         };
         std::vector<std::thread> team;
@@ -894,8 +907,29 @@ int main(int nargs, char* args[]) {
             if (o.saveLogOdds && fdr_logodds_write(o.out_dir, fbase, posMax, negMax, posAll, negAll, P, negN, o.mops, o.zoops,
                                                    o.savePvalues, err)) die(err);
             FdrResult res;
-            fdr_statistics(posMax, negMax, posAll, negAll, P, negN, updatedQ, o.mops, o.zoops, o.savePvalues, res);
-            if (fdr_write(o.out_dir, fbase, res, P, negN, o.mops, o.zoops, o.savePRs, o.savePvalues, err)) die(err);
+            bamm_fdr* const fdr = fdr_handles[n];
+            const bool host_mops = o.mops && !fdr;
+            fdr_statistics(posMax, negMax, posAll, negAll, P, negN, updatedQ, host_mops, o.zoops, o.savePvalues, res);
+            if (fdr_write(o.out_dir, fbase, res, P, negN, host_mops, o.zoops, o.savePRs, o.savePvalues, err)) die(err);
+            if (fdr) {                                        // the MOPS half where the scores are: rows and p-values arrive chunk by chunk
+                uint64_t n_pos = 0, n_neg = 0, n_rows = 0;
+                float occ_mult = 0.f;
+                if (bamm_fdr_statistics(fdr, P, negN, o.savePvalues ? 1 : 0) || bamm_fdr_info(fdr, &n_pos, &n_neg, &n_rows, nullptr, &occ_mult)) die_abi("MOPS statistics");
+                auto rows = [&](uint64_t b, uint64_t e, float* tp, float* fp, float* fd, float* rec, std::string& msg) {
+                    if (bamm_fdr_rows(fdr, b, e, tp, fp, fd, rec)) { msg = std::string("Error: MOPS statistics: ") + bamm_last_error(); return 1; }
+                    return 0;
+                };
+                auto pvals = [&](uint64_t b, uint64_t e, float* p, std::string& msg) {
+                    if (bamm_fdr_pvalues(fdr, b, e, p)) { msg = std::string("Error: MOPS p-values: ") + bamm_last_error(); return 1; }
+                    return 0;
+                };
+                if (fdr_write_mops_chunked(o.out_dir, fbase, occ_mult, n_rows, rows, n_pos, pvals, o.savePRs, o.savePvalues, err)) die(err);
+                bamm_fdr_destroy(fdr);
+                fdr_handles[n] = nullptr;
+                if (timing) std::cerr << "[timing-beside] MOPS statistics on the device: " << n_pos << " + " << n_neg << " window scores, " << n_rows << " rows, "
+                                      << (o.savePRs ? n_rows * 16 : 0) + (o.savePvalues ? n_pos * 4 : 0) + 16
+                                      << " bytes downloaded (computed: 16 per row written, 4 per p-value written, the 16-byte peak)" << std::endl;
+            }
             stage("--FDR: PR / p-value statistics + writers (host)");
         }
     }

@@ -416,6 +416,36 @@ int  bamm_occ_get(const bamm_occ* occ, uint64_t* seq, uint32_t* pos, float* scor
                   uint64_t cap);
 int  bamm_occ_destroy(bamm_occ* occ);
 
+/* ------------------------------------------------------------------ FDR --mops statistics */
+/* FDR::calculatePR's MOPS branch and FDR::calculatePvalues (FDR.cpp:156-196, :278-333) over window scores that stay on
+ * the device (csrc/fdr.hip).  A handle collects two lists, positive and negative window scores, in device arrays from
+ * the context's scratch pool; bamm_fdr_statistics sorts them there, walks the merged order in parallel (a merge-path
+ * search per block and per thread) and finds E_TP and idx_max; rows and p-values are computed for the range a call
+ * names and only those cross to the host.  Every number is the host path's (host/fdr.cpp), bit for bit: both evaluate
+ * csrc/fdr_rows.h.  As there, an exhausted list loses every comparison where the reference reads past its end.
+ *   add_set     scores `set` (the sequences with seq_mask[n] != 0; NULL = all) with the scorer's kernels and appends the
+ *               windows' scores behind what earlier calls added: the folds of one motif, each with its own model
+ *   add_scores  appends scores the caller holds
+ *   statistics  posN / negN: the SEQUENCE counts of FDR.cpp:152,164 (mFold, idx_max's initial value); afterwards the
+ *               handle accepts no more scores.  with_pvalues: bamm_fdr_pvalues may be called
+ *   info        scores in each list, rows = min(idx_max, n_pos + n_neg), E_TP, occ_mult = E_TP / posN; any may be NULL
+ *   rows        TP, FP, FDR, recall of rows begin <= i < end <= n_rows; any array may be NULL
+ *   pvalues     the p-value of the ascending positive scores begin <= i < end <= n_pos
+ *   geometry    steps of the walk one thread / one block owns in this build (tests straddle them)
+ * Errors: a set of another context, a sequence shorter than W, more than 2^32 - 1 scores in a list (the sort's index
+ * width), statistics without any score, scores after statistics, a range outside the rows / the positives.       */
+typedef struct bamm_fdr bamm_fdr;
+int  bamm_fdr_create(bamm_ctx* ctx, bamm_fdr** out);
+int  bamm_fdr_add_set(bamm_fdr* fdr, int negative, bamm_seqs* set, const uint8_t* seq_mask, uint32_t K, uint32_t W,
+                      uint32_t bg_order, const float* v_flat, const float* vbg);
+int  bamm_fdr_add_scores(bamm_fdr* fdr, int negative, const float* scores, uint64_t n);
+int  bamm_fdr_statistics(bamm_fdr* fdr, uint64_t posN, uint64_t negN, int with_pvalues);
+int  bamm_fdr_info(const bamm_fdr* fdr, uint64_t* n_pos, uint64_t* n_neg, uint64_t* n_rows, float* e_tp, float* occ_mult);
+int  bamm_fdr_rows(bamm_fdr* fdr, uint64_t begin, uint64_t end, float* tp, float* fp, float* fdr_out, float* rec);
+int  bamm_fdr_pvalues(bamm_fdr* fdr, uint64_t begin, uint64_t end, float* p);
+int  bamm_fdr_geometry(uint32_t* steps_per_thread, uint32_t* steps_per_block);
+int  bamm_fdr_destroy(bamm_fdr* fdr);
+
 /* Sequence::Sequence where the data will live: bamm_pack_codes_seeded + bamm_seqs_upload with the packing done on the
  * device (csrc/prep.hip) -- reverse complement, 2-bit stream, kmer_[i] next to unknown bases term by term with the
  * reference's rand() draws, the exception list.  The draws themselves are taken on the host (libc's one stream, entered
