@@ -227,6 +227,8 @@ struct GrpKernelArgs {
     const uint4* xrec;           // per sequence: x = lo | B<<12 (group ends lo..lo+B-1 need a virtual row), y/z/w = exact y of
                                  // the positions lo-G+1.., ONE bit string of 7-bit fields (10-bit at K = 3; the value Y =
                                  // position before the sequence)
+    const uint2* lane_rec;       // mixed rows only: [launch slots of the bucket][64] lane records (lane_records.h), built once per
+                                 // handle; k_em_mix loads them instead of deriving window and fix-lane codes in every pass
     // K = 3, accumulating pass: the non-zero sums the fix lanes took out of their virtual count rows, logged per
     // wave (8-byte entries: grouped_kernel.h, GrpLogEntry) and folded into single-column bins in the block epilogue
     unsigned long long* fix_log;
@@ -259,6 +261,10 @@ int launch_em_mix(int mclass, bool accum, bool write_r, const GrpKernelArgs& a, 
 int launch_em_mix1(int mclass, bool accum, bool write_r, const GrpKernelArgs& a, uint32_t blocks, uint32_t threads, hipStream_t st);
 int launch_em_grp(int mclass, bool accum, bool write_r, const GrpKernelArgs& a, uint32_t blocks, uint32_t threads,
                   hipStream_t st);
+// lane_records.hip: the lane records of one mixed-row bucket (sv: its launch slots; T groups, the first B narrow) into
+// out[sv.count][64]; num_cus == kPrimeOnly loads the builder's code object and launches nothing
+int launch_mix_records(int mclass, const SeqView& sv, const uint4* xrec, uint32_t W, uint32_t T, uint32_t B, uint2* out,
+                       uint32_t num_cus, hipStream_t st);
 
 struct SeedKernelArgs {          // Motif::initFromPWM's pass over the sequences (seed.hip)
     SeqView  sv;                 // every resident sequence, exceptions of order K

@@ -67,6 +67,7 @@ int bamm_em_destroy(bamm_em* em) {
                     (void*)em->d_mask_r, (void*)em->d_mask_bits, (void*)em->d_mask_hist, (void*)em->d_mask_sel, (void*)em->d_mask_qseq,
                     (void*)em->d_mask_partial_n, (void*)em->d_mask_partial_stat})
         scratch_free(em->ctx, p);                             // set-sized blocks go back to the context, the rest is freed
+    for (uint2* p : em->owned_lane_rec) scratch_free(em->ctx, p);
     for (uint32_t* p : em->owned_idx) (void)hipFree(p);
     if (em->h_status) (void)hipHostFree(em->h_status);
     (void)hipFree(em->d_stop);

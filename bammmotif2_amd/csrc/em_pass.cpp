@@ -73,6 +73,7 @@ int launch_fused(bamm_em* em, const EmBucket& eb, bool accum, bool write_r, EmKe
     a.sparse_cap = 0; a.sparse_wave_bytes = 0;
     ga.e = a;
     ga.xrec = eb.d_xrec;
+    ga.lane_rec = eb.d_lane_rec;
     if (!grp_geometry(em->prm.K, em->prm.W, eb.G, kMClasses[eb.mclass], threads / 64u, accum, accum ? eb.logc : 0u, eb.layout, &ga.g)) {
         set_error("grouped kernel geometry does not fit (K=%u W=%u)", em->prm.K, em->prm.W);
         return BAMM_ERR_UNSUPPORTED;

@@ -63,6 +63,7 @@ struct EmBucket {                // one kernel launch of an EM pass
     uint32_t G = 0;              // its group size
     uint32_t layout = 0;         // table layout (grp_geometry)
     const uint4* d_xrec = nullptr;
+    const uint2* d_lane_rec = nullptr;   // mixed rows: the bucket's lane records (lane_records.h), owned by the handle
     uint32_t blocks = 0, logc = 0, sparse_cap = 0, sparse_bytes = 0;
     double work = 0;
 };
@@ -198,6 +199,7 @@ struct bamm_em {
     uint32_t total_blocks = 0;
     std::vector<bamm::EmBucket> ebuckets;       // launches of one pass (length class x kernel flavour)
     std::vector<uint32_t*> owned_idx;           // index lists made for this handle (capable / other split)
+    std::vector<uint2*> owned_lane_rec;         // lane records of its mixed-row buckets (512 bytes per sequence, from the scratch pool)
     uint32_t threads = 0;
     // column-sliced path (tables beyond the fused kernel's LDS budget)
     bool sliced = false;

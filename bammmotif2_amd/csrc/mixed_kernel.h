@@ -20,13 +20,14 @@
 // Everything else is k_em_grp's: one wavefront per sequence, M positions per lane, per-wave virtual rows for the
 // group ends next to an N exception (Sequence.cpp:38) and for those cut by the EM.cpp:167 edge -- one virtual
 // row index serves both tables --, wave priorities by phase, the straight-line chain.
+//
+// What a lane needs of its sequence apart from the model -- its stream window, the fix lanes' column codes -- is not derived
+// here: it is loaded, one record per lane, built once per handle (lane_records.h).
 #pragma once
-#include "grouped_kernel.h"
+#include "lane_records.h"
 
 namespace bamm {
 namespace {
-
-constexpr uint32_t kMixBj = 6u, kMixNe = 3u, kMixBv = kMixBj + kMixNe;   // virtual rows per wave: exceptions, edge
 
 template <int OFF>
 __device__ __forceinline__ void lds_add_u64_exec_big(uint32_t byte_addr, unsigned long long v, unsigned long long mask) {
@@ -72,8 +73,8 @@ __global__ void __launch_bounds__(THREADS) k_em_mix(GrpKernelArgs ga) {
     const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const uint32_t total_waves = gridDim.x * WAVES;
     uint32_t t = blockIdx.x * WAVES + wave;
-    RawSeqG<M> nxt{};
-    if (t < a.sv.count) nxt = fetch_seq_g<M>(a.sv, ga.xrec, t, lane);
+    MixSeq nxt{};
+    if (t < a.sv.count) nxt = fetch_mix_seq(a.sv, ga.xrec, ga.lane_rec, t, lane);
 
     // ---- block prologue
     // fused update (update_kernel.h): the previous pass's model update runs here, in every block, from the all-reduced
@@ -147,7 +148,6 @@ __global__ void __launch_bounds__(THREADS) k_em_mix(GrpKernelArgs ga) {
     const float one_minus_q = 1.0f - q;
     const uint32_t lane_b = (uint32_t)lane / T, lane_t = (uint32_t)lane - lane_b * T;     // fix-lane roles: (row, group)
     const bool lane_wide = lane_t >= B;
-    const uint32_t lane_G = lane_wide ? 4u : 3u;
     const uint32_t lane_col0 = lane_wide ? 3u * B + 4u * (lane_t - B) : 3u * lane_t;
     const uint32_t vbase5 = R5V0 + wave * kMixBv, vbase6 = R6V0 + wave * kMixBv;
     const uint32_t sg5_base = lds_offset(sg5), sg6_base = lds_offset(sg6);
@@ -175,7 +175,7 @@ __global__ void __launch_bounds__(THREADS) k_em_mix(GrpKernelArgs ga) {
         my_log = reinterpret_cast<GrpLogEntry*>(ga.fix_log) + (size_t)(blockIdx.x * WAVES + wave) * ga.fix_log_cap;
 
     for (; t < a.sv.count; t += total_waves) {
-        const RawSeqG<M> cur = nxt;
+        const MixSeq cur = nxt;
         // Pointers that are needed once per sequence are read again from the kernel-argument segment (scalar loads,
         // scalar cache) instead of living in SGPRs across the whole loop body: the body is 100 SGPRs over budget, and
         // what hipcc spills it parks in VGPR lanes and fetches back with v_readlane -- VALU instructions of a
@@ -185,9 +185,9 @@ __global__ void __launch_bounds__(THREADS) k_em_mix(GrpKernelArgs ga) {
         asm volatile("" : "+s"(kp));                         // opaque per iteration: the loads are not hoisted out of the loop
         if (t + total_waves < a.sv.count) {
             SeqView sv2;
-            sv2.words = kp->e.sv.words; sv2.word_off = kp->e.sv.word_off; sv2.len = kp->e.sv.len; sv2.pos_off = nullptr;
+            sv2.words = nullptr; sv2.word_off = nullptr; sv2.len = kp->e.sv.len; sv2.pos_off = nullptr;
             sv2.exc_off = nullptr; sv2.exc = nullptr; sv2.mask = kp->e.sv.mask; sv2.idx = kp->e.sv.idx; sv2.count = a.sv.count;
-            nxt = fetch_seq_g<M>(sv2, kp->xrec, t + total_waves, lane);
+            nxt = fetch_mix_seq(sv2, kp->xrec, kp->lane_rec, t + total_waves, lane);
         }
         const uint32_t seq = cur.seq;
         if (WRITE_R && (seq < a.seq_begin || seq >= a.seq_end)) continue;
@@ -197,58 +197,26 @@ __global__ void __launch_bounds__(THREADS) k_em_mix(GrpKernelArgs ga) {
         const uint32_t LW1 = L - W + 1u;
         const uint32_t p0 = (uint32_t)lane * M;
 
-        // ---- one 32-bit stream window per lane (it ends at the lane's last position); sE = the window ending at LW1-1
-        uint32_t X, sE;
-        {
-            constexpr int NSEL = RawSeqG<M>::NSEL;
-            const uint32_t wi0 = p0 >> 4;
-            const uint32_t pE = LW1 - 1u, lpE = pE / (uint32_t)M;
-            const uint32_t pe = p0 + (uint32_t)(M - 1);
-            const uint32_t sel = (pe >> 4) - wi0;
-            uint32_t lo = cur.w[1], hi = cur.w[0];
-#pragma unroll
-            for (int c = 1; c < NSEL; c++) {
-                lo = (sel == (uint32_t)c) ? cur.w[c + 1] : lo;
-                hi = (sel == (uint32_t)c) ? cur.w[c] : hi;
-            }
-            X = __builtin_amdgcn_alignbit(hi, lo, 30u - 2u * (pe & 15u));
-            sE = (uint32_t)__builtin_amdgcn_readlane((int)X, (int)lpE) >> (2u * ((uint32_t)(M - 1) - (pE - lpE * (uint32_t)M)));
-        }
-
-        // ---- virtual rows (one index for both tables): B group ends from xlo on next to an exception, the
-        // positions LW1 .. LW1+2 whose groups are cut by the edge.  The fix lanes' reads of the single-column table
-        // are issued first and waited for after the rows of all positions are decoded: the wave is not yet bound
-        // by the LDS pipe here, the round trip is latency it would otherwise sit out.
-        const uint32_t xw = __builtin_amdgcn_readfirstlane(cur.xr.x);
+        // ---- the lane's record (lane_records.h): its 32-bit stream window (it ends at the lane's last position) and, for a
+        // fix lane, the y of its up to four columns -- 7 bits each (Y = none), in ONE register: it lives until the virtual
+        // count rows are read back after the M-step, and the kernel runs at the 128-VGPR limit of a 1024-thread block.
+        // Virtual rows (one index for both tables): B group ends from xlo on next to an exception, the positions
+        // LW1 .. LW1+2 whose groups are cut by the edge.  The fix lanes' reads of the single-column table are issued
+        // first and waited for after the rows of all positions are decoded: the wave is not yet bound by the LDS pipe
+        // here, the round trip is latency it would otherwise sit out.
+        const uint32_t X = cur.rec.x, yfix = cur.rec.y;      // the flag stays in: every use extracts fields or shifts it out
+        const bool fix = (int)yfix < 0;                      // kMixFixBit, the sign: one compare
+        const uint32_t xw = __builtin_amdgcn_readfirstlane(cur.xw);
         const uint32_t Bx = (xw >> 12) & 0xfu;
         const uint32_t xlo = xw & 0xfffu;
         const uint32_t nE = min(kMixNe, L - LW1);
-        // the y of the fix lane's up to four columns, 7 bits each (Y = none), in ONE register: it lives until the virtual
-        // count rows are read back after the M-step, and the kernel runs at the 128-VGPR limit of a 1024-thread block
-        uint32_t yfix = Y | (Y << 7) | (Y << 14) | (Y << 21);
-        const bool fixJ = lane_b < Bx;
-        const bool fixE = lane_b >= kMixBj && lane_b < kMixBj + nE;
-        const bool fix = fixJ || fixE;
         float fs[4] = {1.0f, 1.0f, 1.0f, 1.0f};
         const float* const sfix_now = (ACCUM && kp->fused) ? kp->s_block + (size_t)blockIdx.x * (W * Ys) : kp->e.s;
         if (fix) {
-            const uint32_t pv = fixJ ? xlo + lane_b : LW1 + (lane_b - kMixBj);         // the row's position
-            const uint32_t xfields = xrec_fields<7>(cur.xr.y, cur.xr.z, cur.xr.w, lane_b + 4u - lane_G);     // the fields of the group's columns
 #pragma unroll
             for (int c = 0; c < 4; c++) {
-                uint32_t yc = Y;                                                       // the column's neutral entry
                 const uint32_t colc = min(lane_col0 + (uint32_t)c, W - 1u);
-                if ((uint32_t)c < lane_G) {
-                    const uint32_t pos = pv - (lane_G - 1u) + (uint32_t)c;           // wraps for positions before the sequence
-                    if (fixJ) {                                                        // record fields start at position xlo-3
-                        yc = (xfields >> (7u * (uint32_t)c)) & 0x7fu;
-                    } else {
-                        yc = (sE >> (2u * ((LW1 - 1u - pos) & 15u))) & (Y - 1u);
-                    }
-                    if (pos >= LW1) yc = Y;                                            // EM.cpp:167 (also pos < 0)
-                }
-                yfix = (yfix & ~(0x7fu << (7 * c))) | (yc << (7 * c));
-                fs[c] = sfix_now[__umul24(colc, Ys) + yc];                             // global, through L1 / L2
+                fs[c] = sfix_now[__umul24(colc, Ys) + ((yfix >> (7 * c)) & 0x7fu)];    // global, through L1 / L2
             }
         }
         // Which slots do not take their row from the stream -- beyond the EM.cpp:167 edge (neutral row), a
@@ -428,7 +396,7 @@ __global__ void __launch_bounds__(THREADS) k_em_mix(GrpKernelArgs ga) {
                 }
             }
             const uint32_t ylog = yfix | resident_fill;          // what is left to log: fields still below Y
-            const uint32_t code = lane_t | (ylog << 3);
+            const uint32_t code = lane_t | (ylog << 3);          // (the record's fix-lane flag, bit 31, falls off here)
             if ((~ylog & (Y | (Y << 7) | (Y << 14) | (Y << 21))) == 0u) acc = 0ull;   // nothing left to log (also: a group wholly beyond the edge)
             const unsigned long long nzm = __ballot(acc != 0ull);
             if (acc != 0ull) {

@@ -29,6 +29,8 @@ int prime_bucket(bamm_ctx* c, const bamm_em_params& prm, uint32_t Y, bool sliced
     GrpKernelArgs ga{};
     ga.e = a;
     if (!grp_geometry(prm.K, prm.W, eb.G, kMClasses[eb.mclass], threads / 64u, true, eb.logc, eb.layout, &ga.g)) return BAMM_OK;   // (the launch reports it)
+    if (eb.layout & 8u)                                      // mixed rows: the builder of the lane records is the handle's first launch
+        if (int rc = launch_mix_records(eb.mclass, SeqView{}, nullptr, prm.W, ga.g.T, ga.g.mixB, nullptr, kPrimeOnly, c->stream)) return rc;
     return launch_em_grp(eb.mclass, true, false, ga, kPrimeOnly, threads, c->stream);
 }
 
@@ -180,6 +182,16 @@ int plan_launches(bamm_em* em, bool global_tables, const uint8_t* seq_mask, Prim
                 if ((rc = dev_upload(c, &d, yes.data(), yes.size()))) return rc;
                 em->owned_idx.push_back(d);
                 eb.count = (uint32_t)yes.size(); eb.d_idx = d;
+            }
+            if ((glayout & 8u) && eb.count) {
+                // mixed rows: every lane's stream window and fix-lane codes per launch slot of this bucket, derived once
+                // here instead of in every pass (lane_records.h; 512 bytes per sequence, set-sized: from the scratch pool)
+                uint2* rec = nullptr;
+                if ((rc = scratch_alloc(c, &rec, (size_t)eb.count * 64u))) return rc;
+                em->owned_lane_rec.push_back(rec);
+                if ((rc = launch_mix_records(eb.mclass, make_view(seqs, em->exc, eb.d_idx, eb.count, nullptr), xr->d_xrec, prm->W,
+                                             gg.T, gg.mixB, rec, (uint32_t)std::max(1, c->num_cus), st))) return rc;
+                eb.d_lane_rec = rec;
             }
             eb.work = (double)eb.count * Mcls * 0.6;       // grouped passes cost about 60 % per sequence
             if (eb.count) em->ebuckets.push_back(eb);
