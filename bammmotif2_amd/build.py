@@ -132,7 +132,8 @@ _HANDLES = [os.path.join(CSRC, "handles.h"), os.path.join(CSRC, "prep.h")]
 EXTRA_DEPS = {"prep.hip": [os.path.join(CSRC, "prep.h")], "negs.hip": [os.path.join(CSRC, "negs.h")],
               "ctx.cpp": _HANDLES, "plan.cpp": _HANDLES, "em_pass.cpp": _HANDLES, "em.cpp": _HANDLES, "score.cpp": _HANDLES, "sites.cpp": _HANDLES,
               "occurrences.cpp": _HANDLES + [os.path.join(CSRC, "occ_pvalue.h")],
-              "fdr.hip": [os.path.join(CSRC, "fdr_rows.h")], "fdr_stats.cpp": _HANDLES + [os.path.join(CSRC, "fdr_rows.h")],
+              "fdr.hip": [os.path.join(CSRC, "fdr_rows.h"), os.path.join(CSRC, "sort_key.h")], "occ.hip": [os.path.join(CSRC, "sort_key.h")],
+              "fdr_stats.cpp": _HANDLES + [os.path.join(CSRC, "fdr_rows.h")],
               "seqs.cpp": _HANDLES + [os.path.join(CSRC, "negs.h"), os.path.join(CSRC, "glibc_rand.h")],
               "pack.cpp": [os.path.join(CSRC, "glibc_rand.h"), os.path.join(CSRC, "prep.h")]}
 FLAGS_STAMP = os.path.join(OBJDIR, "flags.txt")

@@ -340,6 +340,16 @@ int launch_fdr_peak(const FdrWalkArgs& a, hipStream_t st);   // partition, block
 int launch_fdr_rows(const FdrWalkArgs& a, uint64_t begin, uint64_t end, float e_tp, float* tp, float* fp, float* fdr, float* rec, hipStream_t st);
 // p[i - begin] for the ascending positives begin <= i < end
 int launch_fdr_pvalues(const float* pos, const float* neg, uint64_t n_neg, uint64_t begin, uint64_t end, float* p, hipStream_t st);
+// two ASCENDING runs (launch_occ_sort's output) merged into the ascending array sorting their concatenation would give, bit for
+// bit; `out` overlaps neither run
+struct FdrMergeArgs {
+    const float* a;              // the lower-numbered run: its element goes first among equal keys
+    const float* b;
+    uint64_t na, nb;
+    float*   out;                // [na + nb]
+    uint64_t* part;              // [ceil((na + nb) / kFdrStepsPerBlock) + 1] elements of `a` in front of each block's first output
+};
+int launch_fdr_merge(const FdrMergeArgs& m, hipStream_t st);
 // dst[seg[s].dst + k] = src[seg[s].src + k] for k < seg[s].len: the windows of one selected sequence out of a whole set's scores
 struct FdrSeg { unsigned long long src, dst; uint32_t len, pad; };
 int launch_fdr_gather(const float* src, float* dst, const FdrSeg* seg, uint32_t n_seg, uint32_t blocks, hipStream_t st);

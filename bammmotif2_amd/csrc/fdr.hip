@@ -23,6 +23,7 @@
 
 #include "common.h"
 #include "fdr_rows.h"
+#include "sort_key.h"
 
 namespace bamm {
 namespace {
@@ -32,14 +33,21 @@ constexpr uint32_t SPT = kFdrStepsPerThread, SPB = kFdrStepsPerBlock;
 // element i of the descending order; beyond the list (never reached with finite scores): a value that loses every comparison
 __device__ __forceinline__ float desc_at(const float* asc, uint64_t n, uint64_t i) { return i < n ? asc[n - 1u - i] : -__builtin_inff(); }
 
-// positives among the first k steps of the walk: the smallest i with NOT pos[i] > neg[k - 1 - i]
-__device__ uint64_t merge_path(const FdrWalkArgs& a, uint64_t k) {
-    uint64_t lo = k > a.n_neg ? k - a.n_neg : 0u, hi = k < a.n_pos ? k : a.n_pos;
+// The diagonal search of a merge of list A (na elements) with list B (nb): how many of the first k elements taken come from
+// A -- the smallest i with NOT a_first(i, k - 1 - i), where a_first(i, j) says that A[i] is taken before B[j].
+template <class I, class F>
+__device__ __forceinline__ I merge_diagonal(I k, I na, I nb, F&& a_first) {
+    I lo = k > nb ? k - nb : 0u, hi = k < na ? k : na;
     while (lo < hi) {
-        const uint64_t mid = lo + ((hi - lo) >> 1);          // lo <= mid < hi <= min(k, n_pos); k - n_neg <= mid: 0 <= k - 1 - mid < n_neg
-        if (desc_at(a.pos, a.n_pos, mid) > desc_at(a.neg, a.n_neg, k - 1u - mid)) lo = mid + 1u; else hi = mid;
+        const I mid = lo + ((hi - lo) >> 1);                 // lo <= mid < hi <= min(k, na); k - nb <= mid: 0 <= k - 1 - mid < nb
+        if (a_first(mid, k - 1u - mid)) lo = mid + 1u; else hi = mid;
     }
     return lo;
+}
+
+// positives among the first k steps of the walk: the smallest i with NOT pos[i] > neg[k - 1 - i]
+__device__ uint64_t merge_path(const FdrWalkArgs& a, uint64_t k) {
+    return merge_diagonal<uint64_t>(k, a.n_pos, a.n_neg, [&](uint64_t i, uint64_t j) { return desc_at(a.pos, a.n_pos, i) > desc_at(a.neg, a.n_neg, j); });
 }
 
 __global__ __launch_bounds__(kFdrThreads) void k_fdr_partition(FdrWalkArgs a) {
@@ -73,12 +81,8 @@ __device__ __forceinline__ Tile tile_open(const FdrWalkArgs& a, uint64_t blk, fl
     __syncthreads();
     t.sP = lds; t.sN = lds + t.na;
     t.d = threadIdx.x * SPT < t.n ? threadIdx.x * SPT : t.n;
-    uint32_t lo = t.d > t.nc ? t.d - t.nc : 0u, hi = t.d < t.na ? t.d : t.na;
-    while (lo < hi) {
-        const uint32_t mid = lo + ((hi - lo) >> 1);          // < na; d - nc <= mid < d: 0 <= d - 1 - mid < nc
-        if (t.sP[mid] > t.sN[t.d - 1u - mid]) lo = mid + 1u; else hi = mid;
-    }
-    t.i = lo; t.j = t.d - lo;
+    t.i = merge_diagonal<uint32_t>(t.d, t.na, t.nc, [&](uint32_t i, uint32_t j) { return t.sP[i] > t.sN[j]; });
+    t.j = t.d - t.i;
     return t;
 }
 
@@ -216,7 +220,74 @@ __global__ __launch_bounds__(kFdrThreads) void k_fdr_gather(const float* __restr
     }
 }
 
+// ---- merge of two ascending runs (launch_occ_sort's output) into one: what sorting their concatenation gives --------------
+// Element k of the output is A[i] or B[k - i] with i from the diagonal search over the sort's own keys (sort_key.h); equal
+// keys take A's element first, and since the sort writes canonical bits (-0 comes out as +0) equal keys are equal bits: the
+// output does not depend on which run an element came from.  Geometry is the walk's: a block owns SPB consecutive outputs,
+// its boundaries come from one search each in global memory (k_fdr_merge_partition), it stages exactly the keys it consumes
+// in LDS, every thread searches its own diagonal there and emits SPT outputs serially -- into registers, then through the
+// same LDS block, so that the stores to global memory are coalesced.
+__device__ __forceinline__ uint64_t merge_blocks(const FdrMergeArgs& m) { return (m.na + m.nb + SPB - 1u) / SPB; }
+
+__global__ __launch_bounds__(kFdrThreads) void k_fdr_merge_partition(FdrMergeArgs m) {
+    const uint64_t g = (uint64_t)blockIdx.x * kFdrThreads + threadIdx.x, total = m.na + m.nb;
+    if (g > merge_blocks(m)) return;
+    const uint64_t k = g * SPB < total ? g * SPB : total;
+    m.part[g] = merge_diagonal<uint64_t>(k, m.na, m.nb, [&](uint64_t i, uint64_t j) { return key_of(m.a[i]) <= key_of(m.b[j]); });
+}
+
+__global__ __launch_bounds__(kFdrThreads) void k_fdr_merge(FdrMergeArgs m) {
+    __shared__ uint32_t lds[SPB];
+    const uint64_t total = m.na + m.nb, k0 = (uint64_t)blockIdx.x * SPB;
+    const uint32_t n = (uint32_t)(total - k0 < SPB ? total - k0 : SPB);
+    const uint64_t ia0 = m.part[blockIdx.x], ia1 = m.part[blockIdx.x + 1u], ib0 = k0 - ia0;   // part[b] <= k0 (the search's upper bound)
+    // keys are totally ordered, so the path advances by at most one per output: 0 <= ia1 - ia0 <= n, ia1 <= na and
+    // ib0 + (n - (ia1 - ia0)) = k0 + n - ia1 <= nb (the search's lower bound at the next boundary); the clamps restate it
+    uint32_t na = (uint32_t)(ia1 > ia0 ? (ia1 - ia0 < n ? ia1 - ia0 : n) : 0u);
+    if (ia0 + na > m.na) na = (uint32_t)(m.na - ia0);
+    const uint32_t nb = n - na;
+    for (uint32_t x = threadIdx.x; x < n; x += kFdrThreads) {
+        const uint64_t jb = ib0 + (x - na);
+        lds[x] = x < na ? key_of(m.a[ia0 + x]) : (jb < m.nb ? key_of(m.b[jb]) : 0xffffffffu);
+    }
+    __syncthreads();
+    const uint32_t *sA = lds, *sB = lds + na;
+    const uint32_t d = threadIdx.x * SPT < n ? threadIdx.x * SPT : n;
+    uint32_t i = merge_diagonal<uint32_t>(d, na, nb, [&](uint32_t x, uint32_t y) { return sA[x] <= sB[y]; });
+    uint32_t j = d - i;
+    uint32_t out[SPT];
+    uint32_t ka = i < na ? sA[i] : 0u, kb = j < nb ? sB[j] : 0u;     // the heads of the two runs; one LDS read per output refills the taken one
+#pragma unroll
+    for (uint32_t s = 0; s < SPT; s++) {
+        const bool take = i < na && (j >= nb || ka <= kb);
+        out[s] = take ? ka : kb;
+        i += take ? 1u : 0u;
+        j += take ? 0u : 1u;
+        const uint32_t next = take ? i : na + j;             // < n wherever the value is used
+        const uint32_t v = next < n ? lds[next] : 0u;
+        ka = take ? v : ka;
+        kb = take ? kb : v;
+    }
+    __syncthreads();                                         // every thread has read its inputs: the block becomes the output tile
+#pragma unroll
+    for (uint32_t s = 0; s < SPT; s++)
+        if (d + s < n) lds[d + s] = out[s];
+    __syncthreads();
+    for (uint32_t x = threadIdx.x; x < n; x += kFdrThreads) m.out[k0 + x] = float_of(lds[x]);
+}
+
 }  // namespace
+
+int launch_fdr_merge(const FdrMergeArgs& m, hipStream_t st) {
+    const uint64_t total = m.na + m.nb;
+    if (!total) return BAMM_OK;
+    const uint32_t nb = (uint32_t)((total + kFdrStepsPerBlock - 1u) / kFdrStepsPerBlock);   // <= 2^20: a list holds fewer than 2^32 scores
+    int rc;
+    if ((rc = launch_kernel(k_fdr_merge_partition, nb / kFdrThreads + 1u, kFdrThreads, 0, st, m)) ||
+        (rc = launch_kernel(k_fdr_merge, nb, kFdrThreads, 0, st, m))) return rc;
+    BAMM_HIP(hipGetLastError());
+    return BAMM_OK;
+}
 
 int launch_fdr_peak(const FdrWalkArgs& a, hipStream_t st) {
     const uint32_t nb = (uint32_t)a.n_blocks;                // <= 2^21: each list holds fewer than 2^32 scores

@@ -262,11 +262,17 @@ struct bamm_em {
 
 // --FDR --mops statistics (fdr_stats.cpp): the window scores of every fold, positives and negatives, in two device arrays
 // from the context's scratch pool that grow geometrically (a fold's count is not known before it is scored); sorted in
-// place by bamm_fdr_statistics, which also leaves the walk's partition and the peak.
+// place by bamm_fdr_statistics, which also leaves the walk's partition and the peak.  A list is a sequence of pieces, each
+// either an ascending RUN (sorted by bamm_fdr_seal, here or on the handle bamm_fdr_absorb took it from) or OPEN (as the
+// scores arrived); statistics and seal sort the open pieces and merge the runs (k_fdr_merge) instead of sorting them again.
 struct bamm_fdr {
+    struct Piece { uint64_t len; bool run; };
     bamm_ctx* ctx = nullptr;
     float* d[2] = {nullptr, nullptr};           // [0] positives, [1] negatives
     uint64_t n[2] = {0, 0}, cap[2] = {0, 0};
+    std::vector<Piece> pieces[2];               // in the order they lie in d[]; no empty piece, no two open ones in a row; lengths sum to n[]
+    bool sealed = false;                        // each list is one run (or empty): no more scores, may still be absorbed or run statistics
+    bool moved = false;                         // bamm_fdr_absorb emptied it: only destroy is left
     bool done = false, with_pvalues = false;    // statistics ran: no more scores
     uint64_t posN = 0, negN = 0, n_rows = 0;
     float e_tp = 0.0f;

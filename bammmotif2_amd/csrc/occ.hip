@@ -17,23 +17,14 @@
 #include <algorithm>
 
 #include "common.h"
+#include "sort_key.h"
 
 namespace bamm {
 namespace {
 
 constexpr uint32_t kSortThreads = 256, kSortWaves = kSortThreads / 64;
 
-// float bits -> unsigned key in the order of the values; -0 counts as +0 (std::less<float> compares values).  The scorer
-// cannot produce -0 (its sums start from +0, and +0 + -0 = +0): the mapping is for arrays that come from elsewhere.
-__device__ __forceinline__ uint32_t key_of(float x) {
-    uint32_t u = __float_as_uint(x);
-    if (u == 0x80000000u) u = 0u;
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float float_of(uint32_t k) {
-    return __uint_as_float((k & 0x80000000u) ? (k ^ 0x80000000u) : ~k);
-}
-// pass 0 reads the scores themselves, pass 3 writes floats back into the array it started from
+// the keys are sort_key.h's; pass 0 reads the scores themselves, pass 3 writes floats back into the array it started from
 template <int PASS>
 __device__ __forceinline__ uint32_t load_key(const uint32_t* src, uint64_t i) {
     return PASS == 0 ? key_of(__uint_as_float(src[i])) : src[i];

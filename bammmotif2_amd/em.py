@@ -626,7 +626,8 @@ def fdr_geometry():
 
 class FdrMops:
     """FDR::calculatePR's MOPS branch and FDR::calculatePvalues over window scores kept on the device
-    (include/bamm_em.h: bamm_fdr).  Add the folds' scores, call statistics() once, then fetch rows / p-values by range."""
+    (include/bamm_em.h: bamm_fdr).  Add the folds' scores, call statistics() once, then fetch rows / p-values by range.  Folds
+    scored on several contexts: a handle each, seal() them there, absorb() them into the one that runs statistics()."""
 
     def __init__(self, ctx: Context):
         self.ctx, self.lib = ctx, ctx.lib
@@ -644,6 +645,14 @@ class FdrMops:
     def add_scores(self, negative: bool, scores):
         a = np.ascontiguousarray(scores, np.float32)
         check(self.lib.bamm_fdr_add_scores(self.h, 1 if negative else 0, a.ctypes.data_as(C.c_void_p), a.size))
+
+    def seal(self):
+        """Sorts both lists where they lie into one ascending run each; no more scores afterwards."""
+        check(self.lib.bamm_fdr_seal(self.h))
+
+    def absorb(self, other: "FdrMops"):
+        """Moves everything `other` holds (of any context) into this handle; `other` can only be closed afterwards."""
+        check(self.lib.bamm_fdr_absorb(self.h, other.h))
 
     def statistics(self, posN: int, negN: int, with_pvalues: bool = True):
         check(self.lib.bamm_fdr_statistics(self.h, posN, negN, 1 if with_pvalues else 0))

@@ -644,24 +644,36 @@ int main(int nargs, char* args[]) {
     struct FoldOut { std::vector<float> posMax, negMax, posAll, negAll; float q = 0.f; std::string log, err; };
     std::vector<std::vector<FoldOut>> fold_results(seeds.motifs.size());
     // --mops: the window scores of every fold stay where they are scored and the MOPS statistics are computed there
-    // (bamm_fdr, one handle per motif) when all folds run on ONE context; a plan over several contexts, --saveLogOdds
-    // (which prints the scores) and --hostFdr download them and take host/fdr.cpp's path
-    const bool device_fdr = need_gpu && o.FDR && o.mops && !o.hostFdr && !o.saveLogOdds &&
-                            std::all_of(fold_slot.begin(), fold_slot.end(), [&](size_t s) { return s == fold_slot[0]; });
+    // (bamm_fdr): one handle per motif and per slot in use.  With several slots each slot's thread seals its handle when
+    // its folds are done -- the slots sort their scores side by side, beside the other slots' training -- and the runs
+    // are then absorbed, in ascending slot order, by a handle on fold_slot[0]'s context, which merges them; one slot
+    // keeps its one handle and sorts in bamm_fdr_statistics.  --saveLogOdds (which prints the scores) and --hostFdr
+    // download them and take host/fdr.cpp's path
+    const bool device_fdr = need_gpu && o.FDR && o.mops && !o.hostFdr && !o.saveLogOdds;
     std::vector<bamm_fdr*> fdr_handles(seeds.motifs.size(), nullptr);
+    struct FdrPlanTimes { size_t slots = 0, runs = 0; double seal = 0, absorb = 0, merge = 0; };
+    std::vector<FdrPlanTimes> fdr_times(seeds.motifs.size());
     auto run_folds = [&](size_t n, std::vector<FoldOut>& folds) {
         const size_t cv = o.cvFold, P = kept_len.size();
         const Motif& seed = seeds.motifs[n];
         folds.assign(cv, FoldOut());
         for (auto& f : folds) f.q = seed.q;
-        if (device_fdr && bamm_fdr_create(devs[fold_slot[0]].ctx, &fdr_handles[n])) { folds[0].err = bamm_last_error(); return; }
-        bamm_fdr* const fdr = fdr_handles[n];
         std::vector<size_t> slots_in_use;
         for (size_t f = 0; f < cv; f++)
             if (std::find(slots_in_use.begin(), slots_in_use.end(), fold_slot[f]) == slots_in_use.end()) slots_in_use.push_back(fold_slot[f]);
+        std::sort(slots_in_use.begin(), slots_in_use.end());
+        const bool several = slots_in_use.size() > 1;
+        std::vector<bamm_fdr*> slot_fdr(devs.size(), nullptr);   // by slot
+        std::vector<double> slot_seal(devs.size(), 0.0);
+        auto drop_slot_handles = [&] { for (bamm_fdr*& h : slot_fdr) { bamm_fdr_destroy(h); h = nullptr; } };
+        auto seconds_since = [](std::chrono::high_resolution_clock::time_point t) { return std::chrono::duration<double>(std::chrono::high_resolution_clock::now() - t).count(); };
+        if (device_fdr)
+            for (size_t slot : slots_in_use)
+                if (bamm_fdr_create(devs[slot].ctx, &slot_fdr[slot])) { folds[0].err = bamm_last_error(); drop_slot_handles(); return; }
         auto one_fold = [&](size_t fold) {
             Dev& dv = devs[fold_slot[fold]];
             FoldOut& fo = folds[fold];
+            bamm_fdr* const fdr = slot_fdr[fold_slot[fold]];
             Motif m = seed;
             std::vector<uint8_t> train(P, 0), test(P, 0);
             for (size_t i = 0; i + cv <= P; i += cv)         // strided split; the last P mod cv records are unused
@@ -704,8 +716,40 @@ int main(int nargs, char* args[]) {
         };
         std::vector<std::thread> team;
         for (size_t slot : slots_in_use)
-            team.emplace_back([&, slot] { for (size_t f = 0; f < cv; f++) if (fold_slot[f] == slot) one_fold(f); });
+            team.emplace_back([&, slot] {
+                size_t last = cv;
+                for (size_t f = 0; f < cv; f++) if (fold_slot[f] == slot) { one_fold(f); last = f; }
+                if (!several || !slot_fdr[slot] || last == cv || !folds[last].err.empty()) return;
+                const auto t0 = std::chrono::high_resolution_clock::now();
+                if (bamm_fdr_seal(slot_fdr[slot])) folds[last].err = bamm_last_error();
+                slot_seal[slot] = seconds_since(t0);
+            });
         for (auto& t : team) t.join();
+        if (!device_fdr) return;
+        FdrPlanTimes& ft = fdr_times[n];
+        ft.slots = slots_in_use.size();
+        if (!several) { fdr_handles[n] = slot_fdr[slots_in_use[0]]; ft.runs = 1; return; }
+        for (const FoldOut& fo : folds) if (!fo.err.empty()) { drop_slot_handles(); return; }
+        ft.seal = *std::max_element(slot_seal.begin(), slot_seal.end());
+        bamm_ctx* const owner_ctx = devs[fold_slot[0]].ctx;
+        bamm_fdr* owner = nullptr;
+        auto t0 = std::chrono::high_resolution_clock::now();
+        bool ok = bamm_fdr_create(owner_ctx, &owner) == 0;
+        for (size_t slot : slots_in_use) {
+            uint64_t n_pos = 0;
+            if (!ok) break;
+            bamm_fdr_info(slot_fdr[slot], &n_pos, nullptr, nullptr, nullptr, nullptr);
+            ft.runs += n_pos ? 1 : 0;                        // runs of the positive list
+            ok = bamm_fdr_absorb(owner, slot_fdr[slot]) == 0;
+        }
+        ok = ok && bamm_ctx_sync(owner_ctx) == 0;
+        ft.absorb = seconds_since(t0);
+        t0 = std::chrono::high_resolution_clock::now();
+        ok = ok && bamm_fdr_seal(owner) == 0;                // the merge: each list one run, bamm_fdr_statistics finds nothing left to sort
+        ft.merge = seconds_since(t0);
+        if (!ok) { folds[0].err = bamm_last_error(); bamm_fdr_destroy(owner); owner = nullptr; }
+        drop_slot_handles();
+        fdr_handles[n] = owner;
     };
 
     for (size_t n = 0; n < seeds.motifs.size(); n++) {
@@ -926,9 +970,14 @@ int main(int nargs, char* args[]) {
                 if (fdr_write_mops_chunked(o.out_dir, fbase, occ_mult, n_rows, rows, n_pos, pvals, o.savePRs, o.savePvalues, err)) die(err);
                 bamm_fdr_destroy(fdr);
                 fdr_handles[n] = nullptr;
+                if (timing) std::cerr << "[timing-beside] MOPS window scores: device, " << fdr_times[n].runs << " runs from " << fdr_times[n].slots << " slots: seal "
+                                      << fdr_times[n].seal << " s (the slowest slot, beside the other slots' folds), absorb " << fdr_times[n].absorb
+                                      << " s, merge " << fdr_times[n].merge << " s" << std::endl;
                 if (timing) std::cerr << "[timing-beside] MOPS statistics on the device: " << n_pos << " + " << n_neg << " window scores, " << n_rows << " rows, "
                                       << (o.savePRs ? n_rows * 16 : 0) + (o.savePvalues ? n_pos * 4 : 0) + 16
                                       << " bytes downloaded (computed: 16 per row written, 4 per p-value written, the 16-byte peak)" << std::endl;
+            } else if (timing && o.mops) {
+                std::cerr << "[timing-beside] MOPS window scores: host (every fold's scores downloaded, sorted and walked there)" << std::endl;
             }
             stage("--FDR: PR / p-value statistics + writers (host)");
         }

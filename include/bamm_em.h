@@ -432,13 +432,32 @@ int  bamm_occ_destroy(bamm_occ* occ);
  *   rows        TP, FP, FDR, recall of rows begin <= i < end <= n_rows; any array may be NULL
  *   pvalues     the p-value of the ascending positive scores begin <= i < end <= n_pos
  *   geometry    steps of the walk one thread / one block owns in this build (tests straddle them)
+ * Folds that ran on several contexts or devices collect on a handle each and are brought together before statistics:
+ *   seal        sorts both lists where they lie, on the handle's own context, into one ascending RUN each (an empty list
+ *               seals to an empty run) and returns when they are in place; afterwards the handle accepts no more scores
+ *               and cannot absorb, but may be absorbed or run statistics.  A second call is a no-op
+ *   absorb      moves everything `src` holds into `dst`; `src` is empty afterwards and can only be destroyed.  A sealed
+ *               `src` arrives as one more run per list, an unsealed one behind `dst`'s open (unsorted) scores, keeping
+ *               the runs it had absorbed itself.  The handles may belong to different contexts: a device-to-device copy
+ *               on `dst`'s stream behind an event of `src`'s stream, a peer copy between devices, the two contexts'
+ *               pinned staging areas where the devices cannot reach each other; a list that arrives at an empty one on
+ *               its own context brings its block along and nothing is copied.  Blocks come from and go back to the
+ *               respective context's scratch pool
+ *   statistics  (again) sorts what is still open into a run and MERGES each list's runs (two by two, ceil(log2 runs)
+ *               streaming passes) instead of sorting them again.  The sort writes canonical bits (-0 as +0), equal keys
+ *               are equal bits: the merged list is, bit for bit, the sorted concatenation, and every output is what one
+ *               handle given all the scores reports
  * Errors: a set of another context, a sequence shorter than W, more than 2^32 - 1 scores in a list (the sort's index
- * width), statistics without any score, scores after statistics, a range outside the rows / the positives.       */
+ * width), statistics without any score, scores after statistics or seal, a range outside the rows / the positives.
+ * seal and absorb return BAMM_ERR_ARG and leave both handles as they were for: dst == src, a handle past statistics (or
+ * already absorbed), a sealed dst, a list of dst that would exceed 2^32 - 1 scores.                                */
 typedef struct bamm_fdr bamm_fdr;
 int  bamm_fdr_create(bamm_ctx* ctx, bamm_fdr** out);
 int  bamm_fdr_add_set(bamm_fdr* fdr, int negative, bamm_seqs* set, const uint8_t* seq_mask, uint32_t K, uint32_t W,
                       uint32_t bg_order, const float* v_flat, const float* vbg);
 int  bamm_fdr_add_scores(bamm_fdr* fdr, int negative, const float* scores, uint64_t n);
+int  bamm_fdr_seal(bamm_fdr* fdr);
+int  bamm_fdr_absorb(bamm_fdr* dst, bamm_fdr* src);
 int  bamm_fdr_statistics(bamm_fdr* fdr, uint64_t posN, uint64_t negN, int with_pvalues);
 int  bamm_fdr_info(const bamm_fdr* fdr, uint64_t* n_pos, uint64_t* n_neg, uint64_t* n_rows, float* e_tp, float* occ_mult);
 int  bamm_fdr_rows(bamm_fdr* fdr, uint64_t begin, uint64_t end, float* tp, float* fp, float* fdr_out, float* rec);
