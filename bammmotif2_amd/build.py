@@ -222,27 +222,29 @@ def _build_library_locked(force: bool, verbose: bool) -> str:
 HOST = os.path.join(HERE, "host")
 HOST_LIB = os.path.join(HERE, "libbamm_host.so")
 CLI = os.path.join(HERE, "BaMMmotif")
-HOST_SOURCES = ["io.cpp", "fdr.cpp", "hooks.cpp"]
+# one list per product, from which both the compile lines and the staleness check are derived: io.cpp / fdr.cpp and the
+# slot plan are in both, hooks.cpp is the test hooks' own, the other units are the CLI driver (host/driver.h)
+HOST_SHARED = ["io.cpp", "fdr.cpp", "slot_plan.cpp"]
+HOST_SOURCES = HOST_SHARED + ["hooks.cpp"]
+CLI_SOURCES = ["main.cpp", "options.cpp", "context.cpp", "negatives.cpp", "em_run.cpp", "score.cpp", "folds.cpp"] + HOST_SHARED
+HOST_HEADERS = ["bamm_host.h", "slot_plan.h", "options.h", "driver.h"]
 
 
 def build_host(force: bool = False, verbose: bool = False):
     """C++17 host code: libbamm_host.so (test hooks) and the `BaMMmotif` drop-in CLI."""
     build_library(force=False, verbose=verbose)
-    deps = [os.path.join(HOST, f) for f in HOST_SOURCES + ["main.cpp", "bamm_host.h"]] + [os.path.join(CSRC, "occ_pvalue.h"), os.path.join(CSRC, "fdr_rows.h"), LIB]
+    deps = [os.path.join(HOST, f) for f in sorted(set(HOST_SOURCES + CLI_SOURCES)) + HOST_HEADERS] + [os.path.join(CSRC, "occ_pvalue.h"), os.path.join(CSRC, "fdr_rows.h"), LIB]
     outs = [HOST_LIB, CLI]
     if not force and all(os.path.exists(o) for o in outs) and \
             min(os.path.getmtime(o) for o in outs) >= max(os.path.getmtime(d) for d in deps):
         return outs
     cxx = shutil.which("g++") or "g++"
     common = [cxx, "-std=c++17", "-O2", "-fopenmp", "-Wall", "-fPIC", "-L" + HERE, "-Wl,-rpath,$ORIGIN"]
-    cmd = common + ["-shared"] + [os.path.join(HOST, f) for f in HOST_SOURCES] + ["-lbamm_em", "-o", HOST_LIB]
-    if verbose:
-        print(" ".join(cmd))
-    subprocess.check_call(cmd)
-    cmd = common + [os.path.join(HOST, "main.cpp"), os.path.join(HOST, "io.cpp"), os.path.join(HOST, "fdr.cpp"), "-lbamm_em", "-o", CLI]
-    if verbose:
-        print(" ".join(cmd))
-    subprocess.check_call(cmd)
+    for sources, product in ((HOST_SOURCES, ["-shared", "-o", HOST_LIB]), (CLI_SOURCES, ["-o", CLI])):
+        cmd = common + [os.path.join(HOST, f) for f in sources] + ["-lbamm_em"] + product
+        if verbose:
+            print(" ".join(cmd))
+        subprocess.check_call(cmd)
     return outs
 
 

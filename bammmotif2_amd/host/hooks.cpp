@@ -6,6 +6,7 @@
 
 #include <charconv>
 #include "bamm_host.h"
+#include "slot_plan.h"
 #include "../csrc/occ_pvalue.h"
 
 using namespace bammhost;
@@ -262,6 +263,19 @@ int bh_occurrence(const char* dir, const char* base, const uint8_t* codes, const
     std::vector<std::string> headers;
     for (uint64_t n = 0; n < n_seqs; n++) headers.push_back("seq" + std::to_string(n));
     return occurrence_write(dir, base, headers, codes, off, n_seqs, ss != 0, W, p, e, cutoff, g_err);
+}
+
+// the CLI's GPU slot plan (slot_plan.h) as arrays: devices, em_slots, in_em_group and runs_folds hold n_slots entries (the
+// first *n_em of em_slots are set), fold_slot max(1, cv_fold)
+int bh_slot_plan(uint64_t n_slots, uint64_t cv_fold, int em, int fdr, int one_slot_chain, const int* devices, uint64_t* n_em,
+                 uint64_t* em_slots, uint64_t* fold_slot, int* overlap, int* sharded, int* distinct, uint8_t* in_em_group, uint8_t* runs_folds) {
+    const SlotPlan p = make_slot_plan(n_slots, cv_fold, em != 0, fdr != 0, one_slot_chain != 0, std::vector<int>(devices, devices + n_slots));
+    *n_em = p.em_slots.size();
+    std::copy(p.em_slots.begin(), p.em_slots.end(), em_slots);
+    std::copy(p.fold_slot.begin(), p.fold_slot.end(), fold_slot);
+    *overlap = p.overlap; *sharded = p.sharded; *distinct = p.distinct;
+    for (uint64_t d = 0; d < n_slots; d++) { in_em_group[d] = p.in_em_group(d); runs_folds[d] = p.runs_folds(d); }
+    return 0;
 }
 
 }  // extern "C"

@@ -290,7 +290,7 @@ def test_cli_device_packing_and_host_packing_write_the_same_files(tmp_path, gpu_
 @pytest.mark.parametrize("flags", [["--FDR", "-m", "3", "-n", "3", "--saveBaMMs", "--saveInitialBaMMs"], ["--scoreSeqset", "--saveLogOdds"], ["--advanceEM", "--saveBaMMs"]],
                          ids=["fdr", "score", "mask"])
 def test_cli_fast_exit_leaves_the_same_files_as_the_orderly_teardown(flags, tmp_path, gpu_ctx):
-    """The command leaves through _exit(0) once everything is written (host/main.cpp: no destructors, no atexit handlers);
+    """The command leaves through _exit(0) once everything is written (host/context.cpp, leave(): no destructors, no atexit handlers);
     --debug takes the orderly way out.  Every output file byte for byte: a writer still holding a buffer at the fast exit
     would show here (round-4 advice)."""
     build.build_host()
