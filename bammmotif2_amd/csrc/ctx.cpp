@@ -2,6 +2,7 @@
 // the caller's memory and the device goes through, the scratch pool that hands set-sized blocks from one handle to the next.
 // Host code only.
 
+#include <atomic>
 #include <climits>
 #include <type_traits>
 #include <variant>
@@ -13,6 +14,9 @@ namespace bamm {
 constexpr size_t kScratchMinBytes = size_t(4) << 20;         // smaller blocks are plain allocations
 static std::mutex g_ctx_mu;
 static std::vector<bamm_ctx*> g_ctxs;                                // live contexts (flush_idle_scratch walks them)
+// device blocks handed to an owner (dev_alloc_bytes, scratch_alloc_bytes) and not yet taken back (scratch_free); a pool's
+// idle blocks are nobody's.  Read by bamm_device_blocks_live alone: the tests' check that a handle returned all it took.
+static std::atomic<long long> g_blocks_live{0};
 
 static bool flush_idle_scratch(int device) {
     bool any = false;
@@ -41,6 +45,7 @@ int dev_alloc_bytes(void** p, size_t bytes) {
         *p = nullptr;
         return BAMM_ERR_HIP;
     }
+    g_blocks_live++;
     return BAMM_OK;
 }
 
@@ -142,9 +147,12 @@ int scratch_alloc_bytes(bamm_ctx* c, void** p, size_t bytes) {
     if (!got) {
         if (int rc = dev_alloc_bytes(&got, bytes)) return rc;
         got_bytes = bytes;
+    } else {
+        g_blocks_live++;                                     // (a block that was idle; dev_alloc_bytes counted the others)
     }
     if (c->scratch_poison && hipMemsetAsync(got, 0xff, got_bytes, c->stream) != hipSuccess) {
         (void)hipFree(got);
+        g_blocks_live--;
         set_error("hipMemsetAsync failed");
         return BAMM_ERR_HIP;
     }
@@ -160,6 +168,7 @@ int scratch_alloc_bytes(bamm_ctx* c, void** p, size_t bytes) {
 // work on the context's own stream is ordered before the next owner's).  Plain allocations are freed.
 void scratch_free(bamm_ctx* c, void* p) {
     if (!p) return;
+    g_blocks_live--;
     std::vector<void*> evict;
     {
         std::lock_guard<std::mutex> l(c->scratch_mu);
@@ -271,6 +280,8 @@ int bamm_ctx_create(int device, void* hip_stream, bamm_ctx** out) {
     *out = c;
     return BAMM_OK;
 }
+
+long long bamm_device_blocks_live(void) { return g_blocks_live.load(); }
 
 int bamm_device_count(int* n) {
     if (!n) { set_error("bamm_device_count: null argument"); return BAMM_ERR_ARG; }

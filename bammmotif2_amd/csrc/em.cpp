@@ -1,7 +1,6 @@
 // The EM handles of the C ABI: create / destroy, E / M / iterate / optimize / mask, the read-outs and the plan,
 // communicator and timing queries.  Host code only -- the plan is plan.cpp's, one pass and one update em_pass.cpp's.
 
-#include <atomic>
 #include <cmath>
 
 #include "handles.h"
@@ -12,7 +11,7 @@ using namespace bamm;
 // EM::mask's materialised r_, the sliced path's d_state after a replay of that pass (both span the whole set), or a
 // scratch block `tmp` owns that the fused / per-column / long-sequence kernels fill for the range.  The handle's pass
 // counters and event bookkeeping stay as they were.
-int bamm::dense_r_on_device(bamm_em* em, uint64_t begin, uint64_t end, DevTemps& tmp, DenseR* out) {
+int bamm::dense_r_on_device(bamm_em* em, uint64_t begin, uint64_t end, DevBlocks& tmp, DenseR* out) {
     bamm_seqs* s = em->seqs;
     hipStream_t st = em->ctx->stream;
     const uint64_t base = s->h_pos_off[begin], total = s->h_pos_off[end] - base;
@@ -59,24 +58,11 @@ int bamm_em_destroy(bamm_em* em) {
     if (!em) return BAMM_OK;
     (void)hipSetDevice(em->ctx->device);
     (void)hipStreamSynchronize(em->ctx->stream);
-    for (void* p : {(void*)em->d_vbg, (void*)em->d_A, (void*)em->d_v, (void*)em->d_n, (void*)em->d_s, (void*)em->d_qbuf[0],
-                    (void*)em->d_status, (void*)em->d_trace, (void*)em->d_iteration, (void*)em->d_mask, (void*)em->d_acc_ring,
-                    (void*)em->d_v_alt, (void*)em->d_llh[0], (void*)em->d_s_block, (void*)em->d_nnz, (void*)em->d_upd_partial, (void*)em->d_upd_ticket,
-                    (void*)em->d_state, (void*)em->d_list_r, (void*)em->d_list_p, (void*)em->d_list_n, (void*)em->d_s_alt, (void*)em->d_fix_log,
-                    (void*)em->d_qbuf[1], (void*)em->d_qbuf[2],
-                    (void*)em->d_mask_r, (void*)em->d_mask_bits, (void*)em->d_mask_hist, (void*)em->d_mask_sel, (void*)em->d_mask_qseq,
-                    (void*)em->d_mask_partial_n, (void*)em->d_mask_partial_stat})
-        scratch_free(em->ctx, p);                             // set-sized blocks go back to the context, the rest is freed
-    for (uint2* p : em->owned_lane_rec) scratch_free(em->ctx, p);
-    for (uint32_t* p : em->owned_idx) (void)hipFree(p);
-    if (em->h_status) (void)hipHostFree(em->h_status);
-    (void)hipFree(em->d_stop);
-    (void)hipFree(em->d_peer_words);
-    (void)hipFree(em->d_comm_words);
     for (hipEvent_t e : em->opt_events) if (e) (void)hipEventDestroy(e);
     for (auto& ev : em->events) { (void)hipEventDestroy(ev.first); (void)hipEventDestroy(ev.second); }
+    if (em->h_status) (void)hipHostFree(em->h_status);
     bamm_seqs_destroy(em->seqs);
-    delete em;
+    delete em;                                               // its device blocks: set-sized ones go back to the context, the rest is freed
     return BAMM_OK;
 }
 
@@ -94,9 +80,7 @@ int bamm_em_create(bamm_ctx* c, bamm_seqs* seqs, const bamm_em_params* prm, cons
     }
     const uint32_t Y = (uint32_t)ipow4(prm->K + 1);
     BAMM_HIP(hipSetDevice(c->device));
-    bamm_em* em = new bamm_em();
-    em->ctx = c;
-    em->seqs = seqs;
+    bamm_em* em = new bamm_em(c, seqs);
     { std::lock_guard<std::mutex> lock(seqs->mu); seqs->refs++; }
     em->prm = *prm;
     if (em->prm.max_iterations == 0) em->prm.max_iterations = 1000;
@@ -110,26 +94,26 @@ int bamm_em_create(bamm_ctx* c, bamm_seqs* seqs, const bamm_em_params* prm, cons
     Primers primers;                                         // plan_launches starts them; joined on every way out
     auto fail = [&](int code) { bamm_em_destroy(em); return code; };
     if ((rc = exceptions_for_order(seqs, prm->K, &em->exc))) return fail(rc);
-    if ((rc = dev_upload(c, &em->d_vbg, vbg, bg_size(prm->bg_order)))) return fail(rc);
-    if ((rc = dev_upload(c, &em->d_A, A, (size_t)(prm->K + 1) * prm->W))) return fail(rc);
-    if ((rc = dev_upload(c, &em->d_v, v_init, em->vsz))) return fail(rc);
-    if ((rc = dev_alloc(&em->d_n, em->vsz))) return fail(rc);
-    if ((rc = dev_alloc(&em->d_s, (size_t)prm->W * (Y + 1)))) return fail(rc);
-    if ((rc = dev_alloc(&em->d_s_alt, (size_t)prm->W * (Y + 1)))) return fail(rc);
+    if ((rc = em->mem.upload(&em->d_vbg, vbg, bg_size(prm->bg_order)))) return fail(rc);
+    if ((rc = em->mem.upload(&em->d_A, A, (size_t)(prm->K + 1) * prm->W))) return fail(rc);
+    if ((rc = em->mem.upload(&em->d_v, v_init, em->vsz))) return fail(rc);
+    if ((rc = em->mem.alloc(&em->d_n, em->vsz))) return fail(rc);
+    if ((rc = em->mem.alloc(&em->d_s, (size_t)prm->W * (Y + 1)))) return fail(rc);
+    if ((rc = em->mem.alloc(&em->d_s_alt, (size_t)prm->W * (Y + 1)))) return fail(rc);
     for (auto& slot : em->d_qbuf)
-        if ((rc = dev_upload(c, &slot, &prm->q, 1))) return fail(rc);
+        if ((rc = em->mem.upload(&slot, &prm->q, 1))) return fail(rc);
     em->d_q = em->d_qbuf[0];
-    if ((rc = dev_alloc(&em->d_status, 8))) return fail(rc);
-    if ((rc = dev_alloc(&em->d_trace, (size_t)em->prm.max_iterations * 3))) return fail(rc);
-    if ((rc = dev_alloc(&em->d_iteration, 1))) return fail(rc);
+    if ((rc = em->mem.alloc(&em->d_status, 8))) return fail(rc);
+    if ((rc = em->mem.alloc(&em->d_trace, (size_t)em->prm.max_iterations * 3))) return fail(rc);
+    if ((rc = em->mem.alloc(&em->d_iteration, 1))) return fail(rc);
     em->acc_stride = (em->cells + 3 + 1) & ~(size_t)1;      // slots start on 16-byte boundaries
-    if ((rc = dev_alloc(&em->d_acc_ring, 3 * em->acc_stride))) return fail(rc);
+    if ((rc = em->mem.alloc(&em->d_acc_ring, 3 * em->acc_stride))) return fail(rc);
     em->d_acc = em->d_acc_ring;
-    if ((rc = dev_alloc(&em->d_v_alt, em->vsz))) return fail(rc);
-    if ((rc = dev_alloc(&em->d_llh[0], 2))) return fail(rc);
+    if ((rc = em->mem.alloc(&em->d_v_alt, em->vsz))) return fail(rc);
+    if ((rc = em->mem.alloc(&em->d_llh[0], 2))) return fail(rc);
     em->d_llh[1] = em->d_llh[0] + 1;
     if (!update_fits_lds(prm->K, prm->W) && c->use_update_blocks) {
-        if ((rc = dev_alloc(&em->d_upd_partial, kUpdateMaxBlocks)) || (rc = dev_alloc(&em->d_upd_ticket, 1))) return fail(rc);
+        if ((rc = em->mem.alloc(&em->d_upd_partial, kUpdateMaxBlocks)) || (rc = em->mem.alloc(&em->d_upd_ticket, 1))) return fail(rc);
         if (hipMemsetAsync(em->d_upd_ticket, 0, sizeof(uint32_t), st) != hipSuccess) { set_error("hipMemsetAsync failed"); return fail(BAMM_ERR_HIP); }
     }
     {   // counts are sums of r * 2^fix_shift over at most n_seqs_global (else this handle's) sequences, each
@@ -148,7 +132,7 @@ int bamm_em_create(bamm_ctx* c, bamm_seqs* seqs, const bamm_em_params* prm, cons
         return fail(BAMM_ERR_HIP);
     }
     if (seq_mask && seqs->n)
-        if ((rc = dev_upload(c, &em->d_mask, seq_mask, seqs->n))) return fail(rc);
+        if ((rc = em->mem.upload(&em->d_mask, seq_mask, seqs->n))) return fail(rc);
     em->n_active = seqs->n;
     if (seq_mask) em->n_active = (uint64_t)std::count_if(seq_mask, seq_mask + seqs->n, [](uint8_t m) { return m != 0; });
     if (hipHostMalloc((void**)&em->h_status, 24 * sizeof(float) + 16 * sizeof(unsigned long long), hipHostMallocDefault) != hipSuccess) {
@@ -254,8 +238,8 @@ int bamm_em_set_reduce_buffer(bamm_em* em, void* dev_ptr, uint64_t n_words) {
     }
     BAMM_HIP(hipSetDevice(em->ctx->device));
     BAMM_HIP(hipStreamSynchronize(em->ctx->stream));
-    (void)hipFree(em->d_acc_ring);                           // a caller-owned accumulator is one slot: no fused updates
-    em->d_acc_ring = nullptr; em->acc_cur = 0; em->ring_prev_dirty = false; em->fusable = false;
+    em->mem.release(em->d_acc_ring);                         // a caller-owned accumulator is one slot: no fused updates
+    em->acc_cur = 0; em->ring_prev_dirty = false; em->fusable = false;
     em->d_acc = static_cast<long long*>(dev_ptr);
     em->acc_external = true;
     em->acc_dirty = false;
@@ -272,8 +256,7 @@ int bamm_em_update(bamm_em* em) {
 int bamm_em_iterate(bamm_em* em, uint32_t n) {
     if (!em) { set_error("null em"); return BAMM_ERR_ARG; }
     if (int vrc = verify_comm(em)) return vrc;
-    em->events_used = 0; em->pass_no = 0; em->region_open = false;
-    TimedRegionCloser closer{em};                            // (an error return)
+    TimedRegion region(em);                                  // (closes on an error return as well)
     // fusable handles: the update of pass i runs in the prologue of pass i+1's first kernel (one launch and one
     // collective per iteration); the last pass's update is a k_update launch, so the handle is in the same state
     // at every API boundary whichever way its updates ran
@@ -290,8 +273,7 @@ int bamm_em_iterate(bamm_em* em, uint32_t n) {
 int bamm_em_optimize(bamm_em* em, uint32_t* iterations) {
     if (!em) { set_error("null em"); return BAMM_ERR_ARG; }
     if (int vrc = verify_comm(em)) return vrc;
-    em->events_used = 0; em->pass_no = 0; em->region_open = false;
-    TimedRegionCloser closer{em};
+    TimedRegion region(em);
     if (iterations) *iterations = 0;
     const uint32_t max_it = em->prm.max_iterations;
     if (max_it == 0) return BAMM_OK;
@@ -309,15 +291,15 @@ int bamm_em_optimize(bamm_em* em, uint32_t* iterations) {
     // unit u is.  Fusable handles (update_kernel.h): unit u = [update(u-1) in the prologue of] pass u + all-reduce,
     // and one last unit max_it + 1 = k_update(max_it); status(u) is there when unit u + 1 is (lag 1).  A fused
     // update that fires the rule ends every block of its kernel before the pass: same model, same trace.
-    if (!em->d_stop && (rc = dev_alloc(&em->d_stop, 1))) return rc;
+    if (!em->d_stop && (rc = em->mem.alloc(&em->d_stop, 1))) return rc;
     for (hipEvent_t& e : em->opt_events)
         if (!e) BAMM_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
     BAMM_HIP(hipMemsetAsync(em->d_stop, 0, sizeof(uint32_t), st));
     const uint32_t lag = em->fusable ? 1u : 0u;
     const uint32_t units = max_it + lag;
     // The status of update i reaches the host through pinned memory the update's writer stores into (UpdateArgs::
-    // status_mirror) as six self-validating words tagged with i: the host POLLS them.  An event per unit, which this loop
-    // used to record and wait for, costs the stream 4 us per pass (optimize() against iterate(): +4.5 us at every size up to
+    // status_mirror) as six self-validating words tagged with i: the host POLLS them (wait_update_status).  An event per unit, which
+    // this loop used to record and wait for, costs the stream 4 us per pass (optimize() against iterate(): +4.5 us at every size up to
     // 50k sequences, profiles/r05_optimize_vs_iterate.txt); events remain the fallback where the mirror could not be mapped.
     const bool poll = em->d_status_mirror != nullptr;
     if (poll) memset(em->h_tagged, 0, 16 * sizeof(unsigned long long));         // no tag of an earlier call (tags start at 1)
@@ -357,40 +339,8 @@ int bamm_em_optimize(bamm_em* em, uint32_t* iterations) {
             if ((rc = enqueue_unit(enqueued + 1u))) return leave(rc);
             enqueued++;
         }
-        const float* hs = em->h_status + 8 + 8 * (done & 1u);
-        float polled[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        if (poll) {
-            const volatile unsigned long long* slot = em->h_tagged + 8 * (done & 1u);
-            auto arrived = [&] {
-                for (int i = 0; i < 6; i++) {
-                    const unsigned long long w = slot[i];
-                    if ((uint32_t)(w >> 32) != done) return false;
-                    const uint32_t bits = (uint32_t)w;
-                    memcpy(&polled[i], &bits, sizeof(float));
-                }
-                return true;
-            };
-            hs = polled;
-            for (uint32_t spins = 1;; spins++) {
-                if (arrived()) break;
-                if ((spins & 2047u) == 0u) {                                    // now and then: is anything still running?
-                    const hipError_t qs = hipStreamQuery(st);
-                    if (qs == hipSuccess) {                                     // the stream is idle: the tag is there, or never will be
-                        if (arrived()) break;
-                        if (int cs = comm_still_sound(em)) return leave(cs);   // (a block gave up waiting for a peer: every later launch did nothing)
-                        set_error("optimize(): pass %u ended without reporting its status (a kernel of the pass failed?)", done);
-                        return leave(BAMM_ERR_HIP);
-                    }
-                    if (qs != hipErrorNotReady) { (void)hipGetLastError(); set_error("optimize(): %s", hipGetErrorString(qs)); return leave(BAMM_ERR_HIP); }
-                    if (em->comm && comm_aborted(em->comm)) { set_error("the communicator was aborted while optimize() was waiting for pass %u", done); return leave(BAMM_ERR_COMM); }
-                }
-                __builtin_ia32_pause();
-            }
-            std::atomic_thread_fence(std::memory_order_acquire);
-        } else if (hipEventSynchronize(em->opt_events[(done + lag) & 1u]) != hipSuccess) {
-            set_error("hipEventSynchronize failed in optimize()");
-            return leave(BAMM_ERR_HIP);
-        }
+        float hs[8];
+        if ((rc = wait_update_status(em, done, done + lag, hs))) return leave(rc);
         const float llh_prev = llh;
         llh = hs[0];
         const float v_diff = hs[1];
@@ -402,7 +352,7 @@ int bamm_em_optimize(bamm_em* em, uint32_t* iterations) {
             if (!iterate) {
                 // whatever was enqueued behind update(done) found the flag raised and did nothing: back to the snapshot
                 // prepare_update took right after update(done) (buffers, iteration count, kernel-timing samples)
-                restore_book(em, em->books[(first_update + done) & 3u]);
+                em->book() = em->books[(first_update + done) & 3u];
                 if (lag) em->acc_dirty = true;                              // the ring slot the fused update read was never cleared
             }
             break;
@@ -414,11 +364,8 @@ int bamm_em_optimize(bamm_em* em, uint32_t* iterations) {
     return BAMM_OK;
 }
 
-int bamm_em_mask(bamm_em* em, float f, uint32_t* iterations, float* cutoff, uint64_t* listed) {
-    if (!em) { set_error("null em"); return BAMM_ERR_ARG; }
-    if (int vrc = verify_comm(em)) return vrc;
-    bamm_seqs* s = em->seqs;
-    em->pass_summed_in_kernel = false;                       // EM::mask's kernels carry no tail: every one of its sums goes through the communicator
+// ---- EM::mask (EM.cpp:261-503) in stages: checks, plan (plan.cpp: mask_plan), buffers, selection, EM over the listed windows ----
+static int mask_checks(const bamm_em* em, float f) {
     if (!(f > 0.0f && f < 1.0f)) { set_error("bamm_em_mask: fraction %g outside (0,1)", (double)f); return BAMM_ERR_ARG; }
     if (em->n_active == 0) { set_error("bamm_em_mask: no sequences (the reference indexes an empty array, EM.cpp:343)"); return BAMM_ERR_ARG; }
     if (em->prm.W < 2) { set_error("bamm_em_mask: W=1 reads past pos_[n] in the reference (EM.cpp:416)"); return BAMM_ERR_UNSUPPORTED; }
@@ -430,63 +377,33 @@ int bamm_em_mask(bamm_em* em, float f, uint32_t* iterations, float* cutoff, uint
         set_error("bamm_em_mask: the handle has already run E/M passes; the reference calls mask() on a fresh EM only");
         return BAMM_ERR_STATE;
     }
-    if (int rcc = use_device(em->ctx)) return rcc;
-    if (int rcc = clean_accumulator(em)) return rcc;          // sums nobody consumed (bamm_em_accumulate without an update, a getR replay)
-    const size_t kLds = 160 * 1024;
-    const uint32_t W = em->prm.W, Y = em->Y;
-    auto round16 = [](size_t x) { return (x + 15) & ~(size_t)15; };
-    const size_t s_bytes = round16((size_t)W * (Y + 1) * sizeof(float));
-    // M-step: as many columns per launch as fit next to one wave's arrays.  Sequences whose arrays (10 bytes per
-    // position) do not fit beside one column's counts keep them in a global scratch region per wave instead
-    // (~16 000 positions at k = 2; the window lists are 32 bits wide there, so any length goes): slower, same
-    // arithmetic in the same order.  Orders whose count column alone exceeds the LDS (k >= 7) add the listed windows
-    // straight into the pass's accumulator.  The reference has neither limit (EM.cpp:261-503).
-    const bool direct = round16((size_t)Y * 8) > kLds;
-    const bool wave_global = direct || mask_wave_bytes(s->max_len, false) + round16((size_t)Y * 8) > kLds || s->max_len > 65535u;
-    const size_t wave_bytes = mask_wave_bytes(s->max_len, wave_global);
-    if (wave_bytes > 0xffffffffull) { set_error("bamm_em_mask: sequences beyond 2^28 positions"); return BAMM_ERR_UNSUPPORTED; }
-    const bool s_in_lds = s_bytes <= 64 * 1024 && (wave_global || s_bytes + wave_bytes <= kLds);
-    const size_t e_table = s_in_lds ? s_bytes : 0;
-    uint32_t m_cols = direct ? W : (uint32_t)std::min<size_t>(W, (wave_global ? kLds / 2 : std::min(kLds / 2, kLds - wave_bytes)) / ((size_t)Y * 8));
-    m_cols = std::max(1u, m_cols);
-    const size_t m_table = direct ? 0 : round16((size_t)m_cols * Y * 8);
-    auto waves_for = [&](size_t table) {
-        return wave_global ? 4u : (uint32_t)std::max<size_t>(1, std::min<size_t>(4, (kLds - table) / wave_bytes));
-    };
-    const uint32_t init_table = (uint32_t)round16((size_t)W * 4 * sizeof(float));
-    int rc = use_device(em->ctx);
-    if (rc) return rc;
+    return BAMM_OK;
+}
+
+// the handle's EM::mask state (allocated on first use) zeroed, and the kernels' arguments over it
+static int mask_buffers(bamm_em* em, const MaskPlan& p, MaskKernelArgs* out) {
+    bamm_seqs* s = em->seqs;
     hipStream_t st = em->ctx->stream;
-    const uint32_t e_waves = waves_for(e_table), m_waves = waves_for(m_table);
-    // 16 waves per CU (as the fused kernel), but no more partial tables than 64 MiB worth
-    // (arrays in global memory: at most 2048 waves' worth of them)
-    // ... and no more than 8 GiB of them: a launch has at most cus * 8 blocks of 4 waves
-    const uint32_t cus = wave_global ? (uint32_t)std::max<size_t>(1, std::min<size_t>(std::min(64u, (uint32_t)std::max(1, em->ctx->num_cus)), ((size_t)8 << 30) / (32 * wave_bytes)))
-                                     : (uint32_t)std::max(1, em->ctx->num_cus);
-    const uint32_t per_cu = std::max(1u, 16u / std::min(e_waves, m_waves));
-    const uint32_t cap_blocks = direct ? cus * 8u            // no partial tables at all
-                                       : (uint32_t)std::max<size_t>(cus, std::min<size_t>((size_t)cus * per_cu, ((size_t)64 << 20) / (em->cells * 8)));
-    const uint32_t mblocks = std::max(1u, std::min(((uint32_t)s->n + std::min(e_waves, m_waves) - 1) / std::min(e_waves, m_waves), cap_blocks));
+    int rc;
     if (!em->d_mask_r) {
-        em->mask_blocks = mblocks;
-        if ((!direct && (rc = dev_alloc(&em->d_mask_partial_n, (size_t)mblocks * em->cells))) ||
-            (rc = dev_alloc(&em->d_mask_partial_stat, (size_t)mblocks * 4)) ||
-            (rc = scratch_alloc(em->ctx, &em->d_mask_r, (size_t)s->total_len)) ||
-            (rc = dev_alloc(&em->d_mask_bits, (size_t)s->total_len / 32 + 2)) ||
-            (rc = dev_alloc(&em->d_mask_hist, 2049)) || (rc = dev_alloc(&em->d_mask_sel, 1)) ||
-            (em->prm.optimize_q && (rc = dev_alloc(&em->d_mask_qseq, (size_t)s->n))))
+        em->mask_blocks = p.mblocks;
+        if ((!p.direct && (rc = em->mem.alloc(&em->d_mask_partial_n, (size_t)p.mblocks * em->cells))) ||
+            (rc = em->mem.alloc(&em->d_mask_partial_stat, (size_t)p.mblocks * 4)) ||
+            (rc = em->mem.scratch(&em->d_mask_r, (size_t)s->total_len)) ||
+            (rc = em->mem.alloc(&em->d_mask_bits, (size_t)s->total_len / 32 + 2)) ||
+            (rc = em->mem.alloc(&em->d_mask_hist, 2049)) || (rc = em->mem.alloc(&em->d_mask_sel, 1)) ||
+            (em->prm.optimize_q && (rc = em->mem.alloc(&em->d_mask_qseq, (size_t)s->n))))
             return rc;
     }
     BAMM_HIP(hipMemsetAsync(em->d_mask_r, 0, (size_t)s->total_len * sizeof(float), st));
     BAMM_HIP(hipMemsetAsync(em->d_mask_bits, 0, ((size_t)s->total_len / 32 + 2) * sizeof(uint32_t), st));
     BAMM_HIP(hipMemsetAsync(em->d_mask_hist, 0, 2049 * sizeof(long long), st));
     BAMM_HIP(hipMemsetAsync(em->d_mask_sel, 0, sizeof(MaskSelect), st));
-
     MaskKernelArgs a{};
     a.sv = make_view(s, em->exc, nullptr, (uint32_t)s->n, em->d_mask);   // every sequence in natural order
-    a.K = em->prm.K; a.W = W; a.Y = Y;
+    a.K = em->prm.K; a.W = em->prm.W; a.Y = em->Y;
     a.max_len = s->max_len;
-    a.wave_bytes = (uint32_t)wave_bytes;
+    a.wave_bytes = (uint32_t)p.wave_bytes;
     a.v0 = em->d_v; a.vbg0 = em->d_vbg;
     a.q = em->d_q;
     a.q_seq = em->prm.optimize_q ? em->d_mask_qseq : nullptr;
@@ -494,63 +411,85 @@ int bamm_em_mask(bamm_em* em, float f, uint32_t* iterations, float* cutoff, uint
     a.fix_scale = ldexpf(1.0f, (int)em->fix_shift - 40);
     a.r = em->d_mask_r; a.bits = em->d_mask_bits; a.hist = em->d_mask_hist; a.sel = em->d_mask_sel;
     a.partial_n = em->d_mask_partial_n; a.partial_stat = em->d_mask_partial_stat;
-    unsigned char* d_wave = nullptr;
-    DevTemps wave_guard(em->ctx);
-    if (wave_global) {                                       // every launch below has at most cus * 8 blocks of 4 waves
-        if ((rc = wave_guard.scratch(&d_wave, (size_t)std::max(cus * 8u, mblocks) * 4u * wave_bytes))) return rc;
-        a.wave_scratch = d_wave;
-    }
+    *out = a;
+    return BAMM_OK;
+}
 
-    auto blocks_for = [&](uint32_t waves, uint32_t cap) {
-        const uint32_t need = ((uint32_t)s->n + waves - 1) / waves;
-        return std::max(1u, std::min(need, cap));
+// the windows EM::mask trains on: the order-0 pass (EM.cpp:266-323), the cut-off at fraction f in three histogram
+// passes (EM.cpp:329-343), a bit per listed window (EM.cpp:345-356)
+static int mask_select(bamm_em* em, const MaskPlan& p, MaskKernelArgs& a, float f) {
+    hipStream_t st = em->ctx->stream;
+    auto blocks_for = [&](uint32_t waves) {                  // every launch here has at most cus * 8 blocks
+        const uint32_t need = ((uint32_t)em->seqs->n + waves - 1) / waves;
+        return std::max(1u, std::min(need, p.cus * 8));
     };
-    // order-0 pass (EM.cpp:266-323)
-    {
-        a.table_bytes = init_table;
-        const uint32_t waves = waves_for(init_table);
-        if ((rc = launch_mask_init(a, em->prm.optimize_q != 0, blocks_for(waves, cus * 8), waves * 64, st))) return rc;
-    }
-    // cut-off (EM.cpp:329-343)
+    int rc;
+    a.table_bytes = p.init_table;
+    const uint32_t waves = p.waves_for(p.init_table);
+    if ((rc = launch_mask_init(a, em->prm.optimize_q != 0, blocks_for(waves), waves * 64, st))) return rc;
     for (int pass = 0; pass < 3; pass++) {
-        if ((rc = launch_mask_hist(a, pass, blocks_for(4, cus * 8), st))) return rc;
+        if ((rc = launch_mask_hist(a, pass, blocks_for(4), st))) return rc;
         if ((rc = allreduce_words(em, em->d_mask_hist, 2049))) return rc;
         if ((rc = launch_mask_pick(a, pass, f, st))) return rc;
     }
-    if ((rc = launch_mask_bits(a, blocks_for(4, cus * 8), st))) return rc;     // EM.cpp:345-356
+    return launch_mask_bits(a, blocks_for(4), st);
+}
 
-    // EM over the listed windows (EM.cpp:373-494)
-    const int32_t oq = em->prm.optimize_q;
-    em->prm.optimize_q = 0;                                  // q is not touched inside this loop
-    em->events_used = 0; em->pass_no = 0; em->region_open = false;
-    TimedRegionCloser closer{em};
+// EM over the listed windows (EM.cpp:373-494); *iteration = passes run, *llh = the last one's
+static int mask_em_loop(bamm_em* em, const MaskPlan& p, MaskKernelArgs& a, uint32_t* iteration, float* llh) {
+    hipStream_t st = em->ctx->stream;
+    const uint32_t W = em->prm.W;
+    int rc = BAMM_OK;
     bool iterate = true;
-    uint32_t iteration = 0;
-    float llh = em->llh_prev;
-    while (iterate && iteration < em->prm.max_iterations && !rc) {
-        iteration++;
-        const float llh_prev = llh;
+    while (iterate && *iteration < em->prm.max_iterations && !rc) {
+        (*iteration)++;
+        const float llh_prev = *llh;
         a.s = em->d_s;
         a.q = em->d_q;
         if ((rc = record_event(em, true))) break;
-        a.table_bytes = (uint32_t)e_table;
-        rc = launch_mask_e(a, s_in_lds, mblocks, e_waves * 64, st);
-        a.table_bytes = (uint32_t)m_table;
-        for (uint32_t j0 = 0; j0 < W && !rc; j0 += m_cols) {
-            a.j0 = j0; a.j1 = std::min(W, j0 + m_cols);
-            a.acc_direct = direct ? em->d_acc : nullptr;
-            rc = launch_mask_m(a, mblocks, m_waves * 64, st);
+        a.table_bytes = (uint32_t)p.e_table;
+        rc = launch_mask_e(a, p.s_in_lds, p.mblocks, p.e_waves * 64, st);
+        a.table_bytes = (uint32_t)p.m_table;
+        for (uint32_t j0 = 0; j0 < W && !rc; j0 += p.m_cols) {
+            a.j0 = j0; a.j1 = std::min(W, j0 + p.m_cols);
+            a.acc_direct = p.direct ? em->d_acc : nullptr;
+            rc = launch_mask_m(a, p.mblocks, p.m_waves * 64, st);
         }
         if (!rc) rc = record_event(em, false);
-        if (!rc) rc = launch_reduce_partials(direct ? nullptr : em->d_mask_partial_n, em->d_mask_partial_stat, mblocks, W, Y, em->d_acc, st);
+        if (!rc) rc = launch_reduce_partials(p.direct ? nullptr : em->d_mask_partial_n, em->d_mask_partial_stat, p.mblocks, W, em->Y, em->d_acc, st);
         if (!rc) rc = run_allreduce(em);
         if (!rc) rc = run_update(em, false);
         if (!rc) rc = fetch_status(em);
         if (rc) break;
-        llh = em->h_status[0];
+        *llh = em->h_status[0];
         if (em->h_status[1] < em->prm.epsilon) iterate = false;            // EM.cpp:488
-        if (llh - llh_prev < 0 && iteration > 10) iterate = false;         // EM.cpp:489
+        if (*llh - llh_prev < 0 && *iteration > 10) iterate = false;       // EM.cpp:489
     }
+    return rc;
+}
+
+int bamm_em_mask(bamm_em* em, float f, uint32_t* iterations, float* cutoff, uint64_t* listed) {
+    if (!em) { set_error("null em"); return BAMM_ERR_ARG; }
+    if (int vrc = verify_comm(em)) return vrc;
+    em->pass_summed_in_kernel = false;                       // EM::mask's kernels carry no tail: every one of its sums goes through the communicator
+    int rc = mask_checks(em, f);
+    if (rc || (rc = use_device(em->ctx))) return rc;
+    if ((rc = clean_accumulator(em))) return rc;              // sums nobody consumed (bamm_em_accumulate without an update, a getR replay)
+    const MaskPlan p = mask_plan(em->prm.W, em->Y, em->seqs->max_len, em->seqs->n, em->cells, em->ctx->num_cus);
+    if (p.wave_bytes > 0xffffffffull) { set_error("bamm_em_mask: sequences beyond 2^28 positions"); return BAMM_ERR_UNSUPPORTED; }
+    hipStream_t st = em->ctx->stream;
+    MaskKernelArgs a;
+    if ((rc = mask_buffers(em, p, &a))) return rc;
+    DevBlocks wave_guard(em->ctx);
+    if (p.wave_global && (rc = wave_guard.scratch(&a.wave_scratch, p.wave_scratch_bytes))) return rc;
+    if ((rc = mask_select(em, p, a, f))) return rc;
+
+    const int32_t oq = em->prm.optimize_q;
+    em->prm.optimize_q = 0;                                  // q is not touched inside the loop
+    TimedRegion region(em);
+    uint32_t iteration = 0;
+    float llh = em->llh_prev;
+    rc = mask_em_loop(em, p, a, &iteration, &llh);
     em->prm.optimize_q = oq;
     if (rc) return rc;
     em->llh_prev = llh;
@@ -613,7 +552,7 @@ int bamm_em_get_r(bamm_em* em, uint64_t begin, uint64_t end, float* out, uint64_
     if (total == 0) return BAMM_OK;
     BAMM_HIP(hipSetDevice(em->ctx->device));
     hipStream_t st = em->ctx->stream;
-    DevTemps tmp(em->ctx);
+    DevBlocks tmp(em->ctx);
     DenseR dr;
     int rc = dense_r_on_device(em, begin, end, tmp, &dr);
     if (rc) return rc;

@@ -1,6 +1,7 @@
 // One EM pass, one model update and the all-reduce between them: kernel-timing events, the launches of a pass, the
 // update's arguments and the host's bookkeeping of it, the sums over the ranks and the communicator check.  Host code only.
 
+#include <atomic>
 #include <cmath>
 
 #include "handles.h"
@@ -83,8 +84,8 @@ int launch_fused(bamm_em* em, const EmBucket& eb, bool accum, bool write_r, EmKe
         const size_t cap = ((eb.count + waves - 1) / waves) * std::min<size_t>(64, (size_t)ga.g.Bv * ga.g.T);   // entries per wave
         const size_t need = waves * cap;                      // 8-byte entries
         if (need > em->fix_log_words) {
-            if (em->d_fix_log) { scratch_free(em->ctx, em->d_fix_log); em->d_fix_log = nullptr; em->fix_log_words = 0; }
-            if (int rc = scratch_alloc(em->ctx, &em->d_fix_log, need)) return rc;
+            em->mem.release(em->d_fix_log); em->fix_log_words = 0;
+            if (int rc = em->mem.scratch(&em->d_fix_log, need)) return rc;
             em->fix_log_words = need;
         }
         ga.fix_log = em->d_fix_log;
@@ -103,17 +104,6 @@ int launch_fused(bamm_em* em, const EmBucket& eb, bool accum, bool write_r, EmKe
         ga.peer.slot = (uint32_t)(ga.peer.seq % 3ull);
     }
     return launch_em_grp(eb.mclass, accum, write_r, ga, eb.blocks, threads, st);
-}
-
-static EmBook capture_book(const bamm_em* em) {
-    return EmBook{em->d_s, em->d_s_alt, em->d_q, em->d_v, em->d_v_alt, em->s_last, em->q_last, em->d_acc, em->acc_cur, em->llh_cur,
-                  em->host_iteration, em->events_used, em->pass_no, em->estep_done, em->acc_dirty, em->mask_done, em->ring_prev_dirty};
-}
-void restore_book(bamm_em* em, const EmBook& b) {
-    em->d_s = b.d_s; em->d_s_alt = b.d_s_alt; em->d_q = b.d_q; em->d_v = b.d_v; em->d_v_alt = b.d_v_alt;
-    em->s_last = b.s_last; em->q_last = b.q_last; em->d_acc = b.d_acc; em->acc_cur = b.acc_cur; em->llh_cur = b.llh_cur;
-    em->host_iteration = b.host_iteration; em->events_used = b.events_used; em->pass_no = b.pass_no;
-    em->estep_done = b.estep_done; em->acc_dirty = b.acc_dirty; em->mask_done = b.mask_done; em->ring_prev_dirty = b.ring_prev_dirty;
 }
 
 // clear whatever a pass left unconsumed (accumulate without update, getR replay, a fused sequence cut short)
@@ -182,7 +172,7 @@ static void prepare_update(bamm_em* em, bool q_window, bool fused, UpdateArgs& u
     em->llh_cur ^= 1u;
     em->host_iteration++;
     em->estep_done = false;
-    em->books[em->host_iteration & 3u] = capture_book(em);
+    em->books[em->host_iteration & 3u] = em->book();
 }
 
 // local E(+M) pass over every length bucket; every block adds its table into the pass's accumulator.
@@ -216,7 +206,7 @@ int run_accumulate(bamm_em* em, bool accum, bool replay_last, bool dense_r, int 
         if (bk.mclass == kLongClass) {
             // the sliced path's getR() reads dense r from d_state (slot layout unless the E pass is k_em_seq)
             const bool want_r = em->sliced && dense_r;
-            if (want_r && !em->d_state && (rc = scratch_alloc(em->ctx, &em->d_state, (size_t)s->total_len))) return rc;
+            if (want_r && !em->d_state && (rc = em->mem.scratch(&em->d_state, (size_t)s->total_len))) return rc;
             a.r_out = em->d_state;
             if ((rc = launch_long_em(a, accum, want_r, want_r && !em->e_fused, bk.blocks, st))) return rc;
             continue;
@@ -237,7 +227,7 @@ int run_accumulate(bamm_em* em, bool accum, bool replay_last, bool dense_r, int 
             // E kernel took picks the one that runs (the other's launches return at entry).
             const bool adaptive = lists && accum && em->d_nnz && em->adaptive_lists;
             if ((!lists || adaptive) && !em->d_state) {
-                if ((rc = scratch_alloc(em->ctx, &em->d_state, (size_t)s->total_len))) return rc;
+                if ((rc = em->mem.scratch(&em->d_state, (size_t)s->total_len))) return rc;
             }
             auto flavour = [&](bool use_lists, int run_if_long) -> int {   // run_if_long: -1 = unconditional
                 EmKernelArgs f = a;
@@ -347,11 +337,53 @@ int fetch_status(bamm_em* em) {
     return comm_still_sound(em);
 }
 
+// optimize(): the status of the call's update `done` (llh, v_diff, ...) into out[8], once it is there.  Where the update's
+// writer stores it into the pinned mirror (UpdateArgs::status_mirror) as six self-validating words tagged with `done`, the
+// host POLLS them; else it waits for the event recorded behind unit `unit`, whose copy of d_status sits in h_status.
+int wait_update_status(bamm_em* em, uint32_t done, uint32_t unit, float* out) {
+    std::fill(out, out + 8, 0.0f);
+    if (!em->d_status_mirror) {
+        if (hipEventSynchronize(em->opt_events[unit & 1u]) != hipSuccess) {
+            set_error("hipEventSynchronize failed in optimize()");
+            return BAMM_ERR_HIP;
+        }
+        memcpy(out, em->h_status + 8 + 8 * (done & 1u), 8 * sizeof(float));
+        return BAMM_OK;
+    }
+    const volatile unsigned long long* slot = em->h_tagged + 8 * (done & 1u);
+    auto arrived = [&] {
+        for (int i = 0; i < 6; i++) {
+            const unsigned long long w = slot[i];
+            if ((uint32_t)(w >> 32) != done) return false;
+            const uint32_t bits = (uint32_t)w;
+            memcpy(&out[i], &bits, sizeof(float));
+        }
+        return true;
+    };
+    for (uint32_t spins = 1;; spins++) {
+        if (arrived()) break;
+        if ((spins & 2047u) == 0u) {                                    // now and then: is anything still running?
+            const hipError_t qs = hipStreamQuery(em->ctx->stream);
+            if (qs == hipSuccess) {                                     // the stream is idle: the tag is there, or never will be
+                if (arrived()) break;
+                if (int cs = comm_still_sound(em)) return cs;           // (a block gave up waiting for a peer: every later launch did nothing)
+                set_error("optimize(): pass %u ended without reporting its status (a kernel of the pass failed?)", done);
+                return BAMM_ERR_HIP;
+            }
+            if (qs != hipErrorNotReady) { (void)hipGetLastError(); set_error("optimize(): %s", hipGetErrorString(qs)); return BAMM_ERR_HIP; }
+            if (em->comm && comm_aborted(em->comm)) { set_error("the communicator was aborted while optimize() was waiting for pass %u", done); return BAMM_ERR_COMM; }
+        }
+        __builtin_ia32_pause();
+    }
+    std::atomic_thread_fence(std::memory_order_acquire);
+    return BAMM_OK;
+}
+
 // int64 sums of host[0..n) (n <= 4) over the ranks of the handle's communicator, in place: through the handle's own four
 // device words, on the context's stream, synchronised
 static int sum_over_ranks(bamm_em* em, long long* host, size_t n) {
     int rc = use_device(em->ctx);
-    if (!rc && !em->d_comm_words) rc = dev_alloc(&em->d_comm_words, 4);
+    if (!rc && !em->d_comm_words) rc = em->mem.alloc(&em->d_comm_words, 4);
     if (rc) return rc;
     hipStream_t st = em->ctx->stream;
     hipError_t e = hipMemcpyAsync(em->d_comm_words, host, n * sizeof(long long), hipMemcpyHostToDevice, st);
@@ -410,7 +442,7 @@ int verify_comm(bamm_em* em) {
         if ((rc = sum_over_ranks(em, vote, 1))) return rc;
         if (vote[0] == (long long)world) {
             if (!em->d_peer_words) {
-                if ((rc = dev_alloc(&em->d_peer_words, 2))) return rc;
+                if ((rc = em->mem.alloc(&em->d_peer_words, 2))) return rc;
                 BAMM_HIP(hipMemsetAsync(em->d_peer_words, 0, 2 * sizeof(uint32_t), em->ctx->stream));
             }
             em->peer_on = true;

@@ -63,14 +63,14 @@ void fdr_appended(bamm_fdr* h, int which, uint64_t count, bool run) {
 // List `which` as ONE ascending run: every open piece sorted where it lies (launch_occ_sort), then the runs merged two by
 // two, pass by pass, between the list and the second buffer the sort already took from the pool -- ceil(log2 runs)
 // streaming passes; a run without a partner is copied.  The list ends in whichever buffer the last pass wrote.
-int fdr_one_run(bamm_fdr* h, int which, DevTemps& tmp) {
+int fdr_one_run(bamm_fdr* h, int which, DevBlocks& tmp) {
     auto& pieces = h->pieces[which];
     const uint64_t n = h->n[which];
     if (!n || (pieces.size() == 1 && pieces[0].run)) return BAMM_OK;
     bamm_ctx* c = h->ctx;
     hipStream_t st = c->stream;
     int rc;
-    DevTemps sort_tmp(c);                                    // the second buffer goes back to the pool once the launches are queued
+    DevBlocks sort_tmp(c);                                   // the second buffer goes back to the pool once the launches are queued
     uint32_t* d_alt = nullptr;
     if ((rc = sort_tmp.scratch(&d_alt, (size_t)n))) return rc;
     uint64_t at = 0;
@@ -188,7 +188,7 @@ int bamm_fdr_add_set(bamm_fdr* h, int negative, bamm_seqs* set, const uint8_t* s
     if (!total) return BAMM_OK;
     BAMM_HIP(hipSetDevice(c->device));
     if (int rc = fdr_reserve(h, which, total)) return rc;    // refuses a list beyond the sort's index width before anything is scored
-    DevTemps tmp(c);
+    DevBlocks tmp(c);
     DeviceScores sc;
     int rc = score_on_device(c, set, seq_mask, K, W, bg_order, v, vbg, true, true, tmp, &sc);
     if (rc) return rc;
@@ -235,7 +235,7 @@ int bamm_fdr_seal(bamm_fdr* h) {
     BAMM_HIP(hipSetDevice(c->device));
     int rc;
     {
-        DevTemps tmp(c);
+        DevBlocks tmp(c);
         if ((rc = fdr_one_run(h, 0, tmp)) || (rc = fdr_one_run(h, 1, tmp))) return rc;
         BAMM_HIP(hipStreamSynchronize(c->stream));           // the runs are in place when the call returns
     }
@@ -307,7 +307,7 @@ int bamm_fdr_statistics(bamm_fdr* h, uint64_t posN, uint64_t negN, int with_pval
     BAMM_HIP(hipSetDevice(c->device));
     hipStream_t st = c->stream;
     int rc;
-    DevTemps tmp(c);
+    DevBlocks tmp(c);
     if ((rc = fdr_one_run(h, 0, tmp)) || (rc = fdr_one_run(h, 1, tmp))) return rc;
     FdrWalkArgs& w = h->walk;
     w.pos = h->d[0]; w.neg = h->d[1]; w.n_pos = h->n[0]; w.n_neg = h->n[1];
@@ -344,7 +344,7 @@ int bamm_fdr_rows(bamm_fdr* h, uint64_t begin, uint64_t end, float* tp, float* f
     BAMM_HIP(hipSetDevice(c->device));
     float* host[4] = {tp, fp, fdr, rec};
     float* dev[4] = {nullptr, nullptr, nullptr, nullptr};
-    DevTemps tmp(c);
+    DevBlocks tmp(c);
     int rc;
     const uint64_t chunk = std::min(kFdrChunkRows, end - begin);
     for (int k = 0; k < 4; k++)
@@ -365,7 +365,7 @@ int bamm_fdr_pvalues(bamm_fdr* h, uint64_t begin, uint64_t end, float* p) {
     if (!p && end > begin) { set_error("bamm_fdr_pvalues: null argument"); return BAMM_ERR_ARG; }
     bamm_ctx* c = h->ctx;
     BAMM_HIP(hipSetDevice(c->device));
-    DevTemps tmp(c);
+    DevBlocks tmp(c);
     float* d_p = nullptr;
     int rc;
     const uint64_t chunk = std::min(kFdrChunkRows, end - begin);

@@ -2,6 +2,11 @@
 // scratch pool), seqs.cpp (resident sequence sets), plan.cpp (launch plan of an EM handle), em_pass.cpp (one pass, one
 // update, the all-reduce), em.cpp (the EM entry points), score.cpp (the scorer), occurrences.cpp (window p-values) and sites.cpp (windows with r >= cut-off).  Host units only -- no kernel includes it.
 //
+// Who owns what: every device block of a sequence set or an EM handle belongs to the handle's one DevBlocks member
+// (`mem`) from the moment it exists -- the lazily allocated ones, the plan's index lists and lane records, a set's per-order
+// tables alike -- and goes back through scratch_free when the handle is deleted; the d_* pointers only address the blocks.
+// What one model update moves is bamm::EmBook, which bamm_em derives from: optimize()'s snapshot of it is an assignment.
+//
 // Reference seam these replace: class EM (/root/reference/src/refinement/EM.h:11-69,
 // EM.cpp:7-259,505-527) and ScoreSeqSet::calcLogOdds (seq_scoring/ScoreSeqSet.cpp:25-67).
 #pragma once
@@ -68,10 +73,24 @@ struct EmBucket {                // one kernel launch of an EM pass
     double work = 0;
 };
 
-struct EmBook {                   // host-side state one model update moves (optimize() rolls back work that did not happen)
-    float *d_s, *d_s_alt, *d_q, *d_v, *d_v_alt; const float *s_last, *q_last;
-    long long* d_acc; uint32_t acc_cur, llh_cur, host_iteration, events_used, pass_no;
-    bool estep_done, acc_dirty, mask_done, ring_prev_dirty;
+// The host-side state one model update moves -- the part of bamm_em (which derives from it) that optimize() copies after
+// every update and copies back when the stop rule fired behind its look-ahead.  A field an update moves belongs HERE.
+struct EmBook {
+    // the odds table / q the most recent E pass used stay intact for getR() and MStep(): s is double
+    // buffered (only the update writes it), q lives in three slots because EM::optimize_q() may write
+    // it between any two of EStep / MStep / getR (EM.cpp:93-99,505-519) -- see q_write_slot()
+    float *d_s = nullptr, *d_s_alt = nullptr, *d_q = nullptr;
+    float *d_v = nullptr, *d_v_alt = nullptr;   // fused updates read the old v while the writer block stores the new one
+    const float *s_last = nullptr, *q_last = nullptr;
+    long long* d_acc = nullptr;                 // the accumulator slot the current / next pass adds into
+    uint32_t acc_cur = 0;                       // ... its index in the ring (bamm_em::d_acc_ring)
+    uint32_t llh_cur = 0;                       // slot of d_llh the last update wrote
+    uint32_t host_iteration = 0;
+    uint32_t events_used = 0, pass_no = 0;      // kernel-timing samples of the call (bamm_em_set_kernel_timing)
+    bool estep_done = false;
+    bool acc_dirty = false;                     // the accumulator holds sums nobody consumed (accumulate without update, getR replay)
+    bool mask_done = false;                     // getR() serves d_mask_r
+    bool ring_prev_dirty = false;               // the ring slot behind acc_cur was read by a fused update and awaits clearing
 };
 
 }  // namespace bamm
@@ -116,169 +135,6 @@ struct bamm_ctx {
     bool stage_used[2] = {false, false};                     // an enqueued copy still reads (H2D) the chunk: wait for stage_ev first
 };
 
-struct bamm_seqs {
-    bamm_ctx* ctx = nullptr;
-    int refs = 1;
-    std::mutex mu;                              // guards refs and the lazily built per-order tables (handles may be
-                                                // created on one set from several host threads, FDR.cpp:37)
-    uint64_t n = 0, total_len = 0;
-    uint32_t max_len = 0, min_len = 0;
-    uint64_t hbm_bytes = 0;
-    uint32_t* d_words = nullptr;
-    uint64_t* d_word_off = nullptr;
-    uint32_t* d_len = nullptr;
-    uint64_t* d_pos_off = nullptr;
-    std::vector<uint32_t> h_len;
-    bamm::RawVec<uint32_t> h_words;             // host copy of the 2-bit stream (grouped kernel's exception records)
-    std::vector<uint64_t> h_word_off;
-    std::vector<uint64_t> h_pos_off;
-    std::vector<uint64_t> h_exc_off;            // full (11-mer level) exception list
-    bamm::RawVec<uint32_t> h_exc_pos, h_exc_kmer, h_exc_clean;
-    std::vector<bamm::Bucket> buckets;
-    std::map<uint32_t, bamm::ExcK> exc_by_order;   // node-based: pointers into it stay valid
-
-    ~bamm_seqs() {                               // also runs on every error path of bamm_seqs_upload
-        (void)hipFree(d_words);
-        (void)hipFree(d_word_off);
-        (void)hipFree(d_len);
-        (void)hipFree(d_pos_off);
-        for (auto& b : buckets) (void)hipFree(b.d_idx);
-        for (auto& kv : exc_by_order) {
-            (void)hipFree(kv.second.d_off); (void)hipFree(kv.second.d_exc);
-            for (auto& x : kv.second.xrec) (void)hipFree(x.second.d_xrec);
-        }
-    }
-};
-
-struct bamm_em {
-    bamm_ctx* ctx = nullptr;
-    bamm_seqs* seqs = nullptr;
-    bamm_em_params prm{};
-    uint32_t Y = 0, Kbg = 0;
-    size_t vsz = 0, cells = 0;
-    float *d_vbg = nullptr, *d_A = nullptr, *d_v = nullptr, *d_n = nullptr, *d_s = nullptr;
-    float *d_q = nullptr, *d_status = nullptr, *d_trace = nullptr;
-    // the odds table / q the most recent E pass used stay intact for getR() and MStep(): s is double
-    // buffered (only the update writes it), q lives in three slots because EM::optimize_q() may write
-    // it between any two of EStep / MStep / getR (EM.cpp:93-99,505-519) -- see q_write_slot()
-    float *d_s_alt = nullptr;
-    float *d_qbuf[3] = {nullptr, nullptr, nullptr};
-    const float *s_last = nullptr, *q_last = nullptr;
-    uint32_t* d_iteration = nullptr;
-    uint8_t* d_mask = nullptr;
-    // the pass's fused accumulator [cells | llh | sum_r | n_seqs]: 64-bit integers the blocks add into,
-    // summed across ranks as int64 (exact, order-free), consumed and zeroed by the update
-    long long* d_acc = nullptr;                // the slot the current / next pass adds into
-    // ... a ring of three slots when the handle can fuse the model update into the next pass's kernel
-    // (update_kernel.h): pass p adds into slot p mod 3, the next kernel's blocks read it, its writer block clears
-    // the slot after next.  Outside a fused sequence only slot `acc_cur` is ever non-zero.
-    long long* d_acc_ring = nullptr;
-    size_t acc_stride = 0;                      // words per slot
-    uint32_t acc_cur = 0;
-    bool fusable = false;                       // K <= 2-sized tables, first launch of a pass is a grouped kernel with room for the update
-    uint32_t fuse_upd_off = 0;                  // LDS offset of the update's scratch in that kernel
-    float* d_s_block = nullptr;                 // [blocks of the first launch][W * (Y + 1)]
-    float* d_v_alt = nullptr;                   // fused updates read the old v while the writer block stores the new one
-    float* d_llh[2] = {nullptr, nullptr};       // log-likelihood of the last two updates (the stop rule compares them)
-    double* d_upd_partial = nullptr;            // the update spread over blocks (tables beyond its LDS form): v_diff partials
-    uint32_t* d_upd_ticket = nullptr;           // ... and the word its blocks draw tickets from
-    uint32_t llh_cur = 0;                       // slot the last update wrote
-    bool ring_prev_dirty = false;               // the ring slot behind acc_cur was read by a fused update and awaits clearing
-    bool acc_external = false;                 // caller-owned (bamm_em_set_reduce_buffer)
-    bool acc_dirty = false;                    // holds sums nobody consumed (accumulate without update, getR replay)
-    uint32_t fix_shift = 40;                   // counts travel in units of 2^-fix_shift (40 unless the set is huge)
-    float* h_status = nullptr;                  // pinned, 8 floats (+ 2 x 8 for optimize()'s look-ahead where the mirror below is missing)
-    unsigned long long* h_tagged = nullptr;     // ... + 2 x 8 tagged words behind them: what the updates of optimize() report (UpdateArgs::status_mirror)
-    unsigned long long* d_status_mirror = nullptr;   // h_tagged as the device addresses it
-    uint32_t* d_stop = nullptr;                 // optimize(): set by k_update when the stop rule fires
-    const uint32_t* stop_arg = nullptr;         // what the kernels are handed: d_stop inside optimize(), else null
-    hipEvent_t opt_events[2] = {nullptr, nullptr};
-    // this optimize() call's stop rule for k_update (run_update fills UpdateArgs from it)
-    uint32_t opt_iteration = 0;
-    float opt_llh_prev = 0.0f;
-    uint32_t total_blocks = 0;
-    std::vector<bamm::EmBucket> ebuckets;       // launches of one pass (length class x kernel flavour)
-    std::vector<uint32_t*> owned_idx;           // index lists made for this handle (capable / other split)
-    std::vector<uint2*> owned_lane_rec;         // lane records of its mixed-row buckets (512 bytes per sequence, from the scratch pool)
-    uint32_t threads = 0;
-    // column-sliced path (tables beyond the fused kernel's LDS budget)
-    bool sliced = false;
-    std::vector<std::pair<uint32_t, uint32_t>> e_slices, m_slices;
-    uint32_t m_slice_logc = 0;
-    bool e_fused = false;                       // the E pass of the sliced path is k_em_seq (whole odds table in LDS)
-    uint32_t m_slice_cap = 0;                   // sparse list capacity per wave in the M-slices (0 = dense)
-    float* d_state = nullptr;                   // one float per position slot: E-chain state, then r (allocated on first use)
-    // e_fused: the E pass hands the M slices compacted lists of the non-zero windows instead of dense r
-    float* d_list_r = nullptr;
-    uint16_t* d_list_p = nullptr;
-    uint32_t* d_list_n = nullptr;
-    // ... or dense r, chosen per pass on the device: [2] counts of windows with a non-zero addend (the pass before, this pass)
-    unsigned long long* d_nnz = nullptr;
-    uint32_t nnz_prev_slot = 0;
-    unsigned long long nnz_limit = 0;           // above it a pass takes the dense flavour
-    bool adaptive_lists = true;                 // bamm_ctx_set_tuning("adaptive_lists") when the handle was created
-    // K = 3 through the grouped kernel: per-wave log of the virtual rows' counts (grouped_kernel.h), grown on demand
-    unsigned long long* d_fix_log = nullptr;
-    size_t fix_log_words = 0;
-    bamm::ExcK* exc = nullptr;
-    bool estep_done = false;
-    float llh_prev = 0.0f;                      // EM.h:61
-    uint32_t host_iteration = 0;
-    bamm_allreduce_fn allreduce = nullptr;
-    void* allreduce_user = nullptr;
-    bamm_comm* comm = nullptr;                  // native RCCL all-reduce (bamm_em_set_comm)
-    bool comm_verified = false;                 // verify_comm() ran with the peers
-    // in-kernel all-reduce (PeerArgs): the last block of every accumulating pass exchanges the GPU's totals with the peers
-    // and leaves the sum in the accumulator, in place -- no collective launch behind the pass
-    bool peer_on = false;                       // agreed with every rank in verify_comm()
-    bool pass_summed_in_kernel = false;         // the pass just enqueued carried the tail (launch_fused): run_allreduce has nothing to add
-    uint32_t* d_peer_words = nullptr;           // [0] ticket, [1] err
-    long long* d_comm_words = nullptr;          // four words for verify_comm()'s own sums, kept for the handle's life: a hipFree
-                                                // there would synchronise the DEVICE, and with several ranks on one device (the
-                                                // rehearsal forms) a peer that has already launched its first pass spins in that
-                                                // kernel's tail for THIS rank's sums, which this rank cannot launch from inside hipFree
-    std::string peer_note;                      // why peer_on is false although asked for
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> events;
-    uint32_t events_used = 0;
-    uint32_t timing_every = 8, pass_no = 0;     // bamm_em_set_kernel_timing
-    bool timing_now = false;
-    // timing_every == BAMM_TIMING_WHOLE_CALL: ONE pair of events around all the passes of a call
-    bool region_open = false;
-    uint32_t region_passes = 0;
-    std::vector<uint32_t> event_passes;          // passes between the two events of pair i (1 in the per-pass modes)
-    // EM::mask state (allocated on first use)
-    uint64_t n_active = 0;                      // sequences the handle trains on (mask applied)
-    float* d_mask_r = nullptr;                  // responsibilities in the reference layout
-    uint32_t* d_mask_bits = nullptr;
-    long long* d_mask_hist = nullptr;
-    bamm::MaskSelect* d_mask_sel = nullptr;
-    float* d_mask_qseq = nullptr;
-    unsigned long long* d_mask_partial_n = nullptr;
-    double* d_mask_partial_stat = nullptr;
-    uint32_t mask_blocks = 0;
-    bool mask_done = false;                     // getR() serves d_mask_r
-    bamm::EmBook books[4] = {};                 // snapshot right after update i at [i & 3]
-};
-
-// --FDR --mops statistics (fdr_stats.cpp): the window scores of every fold, positives and negatives, in two device arrays
-// from the context's scratch pool that grow geometrically (a fold's count is not known before it is scored); sorted in
-// place by bamm_fdr_statistics, which also leaves the walk's partition and the peak.  A list is a sequence of pieces, each
-// either an ascending RUN (sorted by bamm_fdr_seal, here or on the handle bamm_fdr_absorb took it from) or OPEN (as the
-// scores arrived); statistics and seal sort the open pieces and merge the runs (k_fdr_merge) instead of sorting them again.
-struct bamm_fdr {
-    struct Piece { uint64_t len; bool run; };
-    bamm_ctx* ctx = nullptr;
-    float* d[2] = {nullptr, nullptr};           // [0] positives, [1] negatives
-    uint64_t n[2] = {0, 0}, cap[2] = {0, 0};
-    std::vector<Piece> pieces[2];               // in the order they lie in d[]; no empty piece, no two open ones in a row; lengths sum to n[]
-    bool sealed = false;                        // each list is one run (or empty): no more scores, may still be absorbed or run statistics
-    bool moved = false;                         // bamm_fdr_absorb emptied it: only destroy is left
-    bool done = false, with_pvalues = false;    // statistics ran: no more scores
-    uint64_t posN = 0, negN = 0, n_rows = 0;
-    float e_tp = 0.0f;
-    bamm::FdrWalkArgs walk{};                   // part / block_max / peak: owned, freed with the handle
-};
-
 namespace bamm {
 
 // ---- ctx.cpp ----
@@ -302,24 +158,171 @@ int scratch_alloc(bamm_ctx* c, T** p, size_t count) { return scratch_alloc_bytes
 void scratch_free(bamm_ctx* c, void* p);
 int use_device(const bamm_ctx* c);
 
-// Device memory one call allocates for its own use, freed through scratch_free (pooled blocks go back to the context,
-// the rest is freed) when the owner goes out of scope, or earlier by free_all(); keep() hands a pointer over to whoever
-// takes it, and the owner forgets it.
-struct DevTemps {
+// The owner of device blocks: of a handle's for its life (bamm_seqs::mem, bamm_em::mem), of a call's temporaries for the
+// call.  A block is held from the moment it exists (an upload that fails behind its allocation included) and freed through
+// scratch_free (pooled blocks go back to the context, the rest is freed) when the owner goes out of scope, or earlier by
+// free_all() / release().  keep() hands a pointer over to whoever takes it, and the owner forgets it; adopt() is the same
+// between two owners.
+struct DevBlocks {
     bamm_ctx* c;
     std::vector<void*> held;
-    explicit DevTemps(bamm_ctx* ctx) : c(ctx) {}
-    DevTemps(const DevTemps&) = delete;
-    DevTemps& operator=(const DevTemps&) = delete;
-    ~DevTemps() { free_all(); }
+    explicit DevBlocks(bamm_ctx* ctx) : c(ctx) {}
+    DevBlocks(const DevBlocks&) = delete;
+    DevBlocks& operator=(const DevBlocks&) = delete;
+    ~DevBlocks() { free_all(); }
     template <class T> int alloc(T** p, size_t count) { return hold(p, dev_alloc(p, count ? count : 1)); }
     template <class T> int upload(T** p, const T* host, size_t count) { return hold(p, dev_upload(c, p, host, count)); }
     template <class T> int scratch(T** p, size_t count) { return hold(p, scratch_alloc(c, p, count)); }
     void keep(const void* p) { held.erase(std::remove(held.begin(), held.end(), p), held.end()); }
+    void adopt(DevBlocks& from, void* p) { if (p) held.push_back(p); from.keep(p); }   // (held here before `from` lets go)
+    template <class T> void release(T*& p) { keep(p); scratch_free(c, p); p = nullptr; }   // this one now (nullptr: nothing)
     void free_all() { for (void* p : held) scratch_free(c, p); held.clear(); }
   private:
     template <class T> int hold(T** p, int rc) { if (*p) held.push_back((void*)*p); return rc; }
 };
+
+}  // namespace bamm
+
+struct bamm_seqs {
+    bamm_ctx* ctx = nullptr;
+    bamm::DevBlocks mem;                        // every d_* below, the buckets' index lists and the per-order tables
+    explicit bamm_seqs(bamm_ctx* c) : ctx(c), mem(c) {}      // (its destructor also runs on every error path of bamm_seqs_upload)
+    int refs = 1;
+    std::mutex mu;                              // guards refs and the lazily built per-order tables (handles may be
+                                                // created on one set from several host threads, FDR.cpp:37)
+    uint64_t n = 0, total_len = 0;
+    uint32_t max_len = 0, min_len = 0;
+    uint64_t hbm_bytes = 0;
+    uint32_t* d_words = nullptr;
+    uint64_t* d_word_off = nullptr;
+    uint32_t* d_len = nullptr;
+    uint64_t* d_pos_off = nullptr;
+    std::vector<uint32_t> h_len;
+    bamm::RawVec<uint32_t> h_words;             // host copy of the 2-bit stream (grouped kernel's exception records)
+    std::vector<uint64_t> h_word_off;
+    std::vector<uint64_t> h_pos_off;
+    std::vector<uint64_t> h_exc_off;            // full (11-mer level) exception list
+    bamm::RawVec<uint32_t> h_exc_pos, h_exc_kmer, h_exc_clean;
+    std::vector<bamm::Bucket> buckets;
+    std::map<uint32_t, bamm::ExcK> exc_by_order;   // node-based: pointers into it stay valid
+};
+
+struct bamm_em : bamm::EmBook {                 // (the fields an update moves: d_s, d_q, d_v, d_acc, ... -- see EmBook)
+    bamm_ctx* ctx = nullptr;
+    bamm_seqs* seqs = nullptr;
+    bamm::DevBlocks mem;                        // every device block of the handle, from bamm_em_create's to the lazily allocated ones
+    bamm_em(bamm_ctx* c, bamm_seqs* s) : ctx(c), seqs(s), mem(c) {}
+    bamm::EmBook& book() { return *this; }
+    bamm_em_params prm{};
+    uint32_t Y = 0, Kbg = 0;
+    size_t vsz = 0, cells = 0;
+    float *d_vbg = nullptr, *d_A = nullptr, *d_n = nullptr;
+    float *d_status = nullptr, *d_trace = nullptr;
+    float *d_qbuf[3] = {nullptr, nullptr, nullptr};  // the three slots d_q / q_last point into
+    uint32_t* d_iteration = nullptr;
+    uint8_t* d_mask = nullptr;
+    // the pass's fused accumulator [cells | llh | sum_r | n_seqs] (d_acc): 64-bit integers the blocks add into,
+    // summed across ranks as int64 (exact, order-free), consumed and zeroed by the update
+    // ... a ring of three slots when the handle can fuse the model update into the next pass's kernel
+    // (update_kernel.h): pass p adds into slot p mod 3, the next kernel's blocks read it, its writer block clears
+    // the slot after next.  Outside a fused sequence only slot `acc_cur` is ever non-zero.
+    long long* d_acc_ring = nullptr;
+    size_t acc_stride = 0;                      // words per slot
+    bool fusable = false;                       // K <= 2-sized tables, first launch of a pass is a grouped kernel with room for the update
+    uint32_t fuse_upd_off = 0;                  // LDS offset of the update's scratch in that kernel
+    float* d_s_block = nullptr;                 // [blocks of the first launch][W * (Y + 1)]
+    float* d_llh[2] = {nullptr, nullptr};       // log-likelihood of the last two updates (the stop rule compares them)
+    double* d_upd_partial = nullptr;            // the update spread over blocks (tables beyond its LDS form): v_diff partials
+    uint32_t* d_upd_ticket = nullptr;           // ... and the word its blocks draw tickets from
+    bool acc_external = false;                 // caller-owned (bamm_em_set_reduce_buffer)
+    uint32_t fix_shift = 40;                   // counts travel in units of 2^-fix_shift (40 unless the set is huge)
+    float* h_status = nullptr;                  // pinned, 8 floats (+ 2 x 8 for optimize()'s look-ahead where the mirror below is missing)
+    unsigned long long* h_tagged = nullptr;     // ... + 2 x 8 tagged words behind them: what the updates of optimize() report (UpdateArgs::status_mirror)
+    unsigned long long* d_status_mirror = nullptr;   // h_tagged as the device addresses it
+    uint32_t* d_stop = nullptr;                 // optimize(): set by k_update when the stop rule fires
+    const uint32_t* stop_arg = nullptr;         // what the kernels are handed: d_stop inside optimize(), else null
+    hipEvent_t opt_events[2] = {nullptr, nullptr};
+    // this optimize() call's stop rule for k_update (run_update fills UpdateArgs from it)
+    uint32_t opt_iteration = 0;
+    float opt_llh_prev = 0.0f;
+    uint32_t total_blocks = 0;
+    std::vector<bamm::EmBucket> ebuckets;       // launches of one pass (length class x kernel flavour)
+    uint32_t threads = 0;
+    // column-sliced path (tables beyond the fused kernel's LDS budget)
+    bool sliced = false;
+    std::vector<std::pair<uint32_t, uint32_t>> e_slices, m_slices;
+    uint32_t m_slice_logc = 0;
+    bool e_fused = false;                       // the E pass of the sliced path is k_em_seq (whole odds table in LDS)
+    uint32_t m_slice_cap = 0;                   // sparse list capacity per wave in the M-slices (0 = dense)
+    float* d_state = nullptr;                   // one float per position slot: E-chain state, then r (allocated on first use)
+    // e_fused: the E pass hands the M slices compacted lists of the non-zero windows instead of dense r
+    float* d_list_r = nullptr;
+    uint16_t* d_list_p = nullptr;
+    uint32_t* d_list_n = nullptr;
+    // ... or dense r, chosen per pass on the device: [2] counts of windows with a non-zero addend (the pass before, this pass)
+    unsigned long long* d_nnz = nullptr;
+    uint32_t nnz_prev_slot = 0;
+    unsigned long long nnz_limit = 0;           // above it a pass takes the dense flavour
+    bool adaptive_lists = true;                 // bamm_ctx_set_tuning("adaptive_lists") when the handle was created
+    // K = 3 through the grouped kernel: per-wave log of the virtual rows' counts (grouped_kernel.h), grown on demand
+    unsigned long long* d_fix_log = nullptr;
+    size_t fix_log_words = 0;
+    bamm::ExcK* exc = nullptr;
+    float llh_prev = 0.0f;                      // EM.h:61
+    bamm_allreduce_fn allreduce = nullptr;
+    void* allreduce_user = nullptr;
+    bamm_comm* comm = nullptr;                  // native RCCL all-reduce (bamm_em_set_comm)
+    bool comm_verified = false;                 // verify_comm() ran with the peers
+    // in-kernel all-reduce (PeerArgs): the last block of every accumulating pass exchanges the GPU's totals with the peers
+    // and leaves the sum in the accumulator, in place -- no collective launch behind the pass
+    bool peer_on = false;                       // agreed with every rank in verify_comm()
+    bool pass_summed_in_kernel = false;         // the pass just enqueued carried the tail (launch_fused): run_allreduce has nothing to add
+    uint32_t* d_peer_words = nullptr;           // [0] ticket, [1] err
+    long long* d_comm_words = nullptr;          // four words for verify_comm()'s own sums, kept for the handle's life (never released
+                                                // early): a hipFree there would synchronise the DEVICE, and with several ranks on one
+                                                // device (the rehearsal forms) a peer that has already launched its first pass spins in that
+                                                // kernel's tail for THIS rank's sums, which this rank cannot launch from inside hipFree
+    std::string peer_note;                      // why peer_on is false although asked for
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> events;
+    uint32_t timing_every = 8;                  // bamm_em_set_kernel_timing
+    bool timing_now = false;
+    // timing_every == BAMM_TIMING_WHOLE_CALL: ONE pair of events around all the passes of a call
+    bool region_open = false;
+    uint32_t region_passes = 0;
+    std::vector<uint32_t> event_passes;          // passes between the two events of pair i (1 in the per-pass modes)
+    // EM::mask state (allocated on first use)
+    uint64_t n_active = 0;                      // sequences the handle trains on (mask applied)
+    float* d_mask_r = nullptr;                  // responsibilities in the reference layout
+    uint32_t* d_mask_bits = nullptr;
+    long long* d_mask_hist = nullptr;
+    bamm::MaskSelect* d_mask_sel = nullptr;
+    float* d_mask_qseq = nullptr;
+    unsigned long long* d_mask_partial_n = nullptr;
+    double* d_mask_partial_stat = nullptr;
+    uint32_t mask_blocks = 0;
+    bamm::EmBook books[4] = {};                 // book() right after update i at [i & 3]
+};
+
+// --FDR --mops statistics (fdr_stats.cpp): the window scores of every fold, positives and negatives, in two device arrays
+// from the context's scratch pool that grow geometrically (a fold's count is not known before it is scored); sorted in
+// place by bamm_fdr_statistics, which also leaves the walk's partition and the peak.  A list is a sequence of pieces, each
+// either an ascending RUN (sorted by bamm_fdr_seal, here or on the handle bamm_fdr_absorb took it from) or OPEN (as the
+// scores arrived); statistics and seal sort the open pieces and merge the runs (k_fdr_merge) instead of sorting them again.
+struct bamm_fdr {
+    struct Piece { uint64_t len; bool run; };
+    bamm_ctx* ctx = nullptr;
+    float* d[2] = {nullptr, nullptr};           // [0] positives, [1] negatives
+    uint64_t n[2] = {0, 0}, cap[2] = {0, 0};
+    std::vector<Piece> pieces[2];               // in the order they lie in d[]; no empty piece, no two open ones in a row; lengths sum to n[]
+    bool sealed = false;                        // each list is one run (or empty): no more scores, may still be absorbed or run statistics
+    bool moved = false;                         // bamm_fdr_absorb emptied it: only destroy is left
+    bool done = false, with_pvalues = false;    // statistics ran: no more scores
+    uint64_t posN = 0, negN = 0, n_rows = 0;
+    float e_tp = 0.0f;
+    bamm::FdrWalkArgs walk{};                   // part / block_max / peak: owned, freed with the handle
+};
+
+namespace bamm {
 
 // ---- seqs.cpp ----
 // fn(begin, end) over contiguous ranges of [0, n) on the host threads the process was granted (bamm_set_host_threads):
@@ -350,7 +353,7 @@ struct DeviceScores {
     std::vector<uint64_t> moff;         // [n+1] prefix sums of L-W+1
 };
 int score_on_device(bamm_ctx* c, bamm_seqs* s, const uint8_t* seq_mask, uint32_t K, uint32_t W, uint32_t bg_order, const float* v,
-                    const float* vbg, bool want_mops, bool pooled_mops, DevTemps& tmp, DeviceScores* out);
+                    const float* vbg, bool want_mops, bool pooled_mops, DevBlocks& tmp, DeviceScores* out);
 
 // ---- plan.cpp ----
 uint32_t default_threads(const bamm_ctx* c, int mclass);
@@ -366,6 +369,26 @@ struct Primers {
 bool plan_slices(bamm_em* em);
 // the launches of one pass, their blocks, the fused update and the sliced path's lists; primes each kernel it names
 int plan_launches(bamm_em* em, bool global_tables, const uint8_t* seq_mask, Primers& primers);
+// The launch geometry of bamm_em_mask, a pure function of the model's shape (W, Y = 4^(K+1), cells = W * Y), the set's
+// longest sequence and size, and the device's CUs.  M-step: as many columns per launch as fit next to one wave's arrays.
+// Sequences whose arrays (10 bytes per position) do not fit beside one column's counts keep them in a global scratch
+// region per wave instead (~16 000 positions at k = 2; the window lists are 32 bits wide there, so any length goes):
+// slower, same arithmetic in the same order.  Orders whose count column alone exceeds the LDS (k >= 7) add the listed
+// windows straight into the pass's accumulator.  The reference has neither limit (EM.cpp:261-503).
+struct MaskPlan {
+    bool direct, wave_global;                   // counts straight into the accumulator; per-wave arrays in global scratch
+    size_t wave_bytes;                          // mask_wave_bytes(max_len, wave_global)
+    bool s_in_lds;
+    size_t e_table;                             // LDS table of the E launch (the odds when s_in_lds)
+    uint32_t m_cols;                            // columns per M launch
+    size_t m_table;                             // ... and their count table
+    uint32_t init_table;                        // LDS table of the order-0 pass
+    uint32_t e_waves, m_waves;                  // waves per block
+    uint32_t cus, mblocks;                      // CUs the launches are sized for; blocks of the E / M launches
+    size_t wave_scratch_bytes;                  // the global region of the per-wave arrays (0 unless wave_global)
+    uint32_t waves_for(size_t table) const;     // waves per block beside an LDS table of that size
+};
+MaskPlan mask_plan(uint32_t W, uint32_t Y, uint32_t max_len, uint64_t n_seqs, size_t cells, int num_cus);
 
 // ---- em.cpp ----
 struct DenseR {
@@ -373,15 +396,20 @@ struct DenseR {
     uint64_t base;
     bool slot_layout;            // window start i at slot i+W-1 (the e_slice kernels) instead of the reference's L-W-i
 };
-int dense_r_on_device(bamm_em* em, uint64_t begin, uint64_t end, DevTemps& tmp, DenseR* out);
+int dense_r_on_device(bamm_em* em, uint64_t begin, uint64_t end, DevBlocks& tmp, DenseR* out);
 
 // ---- em_pass.cpp ----
 int record_event(bamm_em* em, bool start);
 int close_timed_region(bamm_em* em);
-struct TimedRegionCloser { bamm_em* em; ~TimedRegionCloser() { (void)close_timed_region(em); } };
+// the kernel-timing samples of one iterate() / optimize() / mask() call: they start afresh with it, and a whole-call
+// interval still open is closed on every way out
+struct TimedRegion {
+    bamm_em* em;
+    explicit TimedRegion(bamm_em* e) : em(e) { em->events_used = 0; em->pass_no = 0; em->region_open = false; }
+    ~TimedRegion() { (void)close_timed_region(em); }
+};
 int launch_fused(bamm_em* em, const EmBucket& eb, bool accum, bool write_r, EmKernelArgs& a, uint32_t threads,
                  hipStream_t st, const UpdateArgs* fuse = nullptr);
-void restore_book(bamm_em* em, const EmBook& b);
 int clean_accumulator(bamm_em* em);
 int run_accumulate(bamm_em* em, bool accum, bool replay_last = false, bool dense_r = false, int fuse_q_window = -1);
 int allreduce_words(bamm_em* em, void* dev_ptr, size_t n_words);
@@ -390,6 +418,8 @@ float* q_write_slot(bamm_em* em);
 int run_update(bamm_em* em, bool q_window);
 int comm_still_sound(const bamm_em* em);
 int fetch_status(bamm_em* em);
+// optimize(): waits until update `done` of the call (enqueued with unit `unit`) has reported, and leaves its status in out[8]
+int wait_update_status(bamm_em* em, uint32_t done, uint32_t unit, float* out);
 int verify_comm(bamm_em* em);
 
 }  // namespace bamm

@@ -42,7 +42,7 @@ int bamm_occurrences(bamm_ctx* c, bamm_seqs* positives, bamm_seqs* negatives, ui
 
     // negatives: score, sort in place, fetch the lowest nTop + 1 (the scorer's per-sequence maxima are outputs its kernels
     // write unconditionally: a few bytes per sequence nobody reads here)
-    DevTemps tmp(c);
+    DevBlocks tmp(c);
     DeviceScores neg;
     if ((rc = score_on_device(c, negatives, nullptr, K, W, bg_order, v, vbg, true, true, tmp, &neg))) return rc;
     {
@@ -50,7 +50,7 @@ int bamm_occurrences(bamm_ctx* c, bamm_seqs* positives, bamm_seqs* negatives, ui
         // positives' scores below) is ordered behind them on the context's one stream.  The small histogram table is a
         // plain allocation and lives to the end of the call -- freeing it here would synchronise the device (as freeing a
         // second buffer below the pool's 4 MB does: a set that small has nothing to overlap with).
-        DevTemps sort_tmp(c);
+        DevBlocks sort_tmp(c);
         uint32_t *d_alt = nullptr, *d_hist = nullptr;
         const uint32_t blocks = occ_sort_blocks((uint32_t)negN, (uint32_t)std::max(1, c->num_cus));
         if ((rc = sort_tmp.scratch(&d_alt, (size_t)negN)) || (rc = tmp.alloc(&d_hist, (size_t)256 * blocks)) ||
@@ -77,7 +77,7 @@ int bamm_occurrences(bamm_ctx* c, bamm_seqs* positives, bamm_seqs* negatives, ui
         unsigned long long found = 0;
         a.cap = std::min<uint64_t>(n_pos, std::max<uint64_t>(65536, n_pos / 256));
         for (int attempt = 0; attempt < 2; attempt++) {      // the list is sized by guess; a launch that counts more runs again with room for all
-            DevTemps list_tmp(c);
+            DevBlocks list_tmp(c);
             if ((rc = list_tmp.scratch(&a.out, (size_t)a.cap))) return rc;
             BAMM_HIP(hipMemsetAsync(a.count, 0, sizeof(unsigned long long), st));
             if ((rc = launch_occ_rank(a, blocks, st)) || (rc = ctx_download(c, &found, a.count, sizeof found))) return rc;

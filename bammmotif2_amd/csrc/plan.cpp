@@ -1,6 +1,6 @@
 // The launch plan of an EM handle (bamm_em_create): the column slices of tables beyond the fused kernel's LDS, the
 // split of every length bucket into grouped-column and per-column launches, the blocks of each launch, the launch that
-// carries the fused update and the sliced path's lists.  Host code only.
+// carries the fused update and the sliced path's lists; the launch geometry of EM::mask.  Host code only.
 
 #include <atomic>
 #include <cmath>
@@ -126,6 +126,7 @@ int plan_launches(bamm_em* em, bool global_tables, const uint8_t* seq_mask, Prim
     // plan, whether most sequences of a class carry exceptions, is the shard's own: a property of the data that holds
     // for every shard alike on double-stranded sets (each sequence has its strand junction) and on clean single-stranded ones.
     const uint64_t plan_n = std::max<uint64_t>(std::max<uint64_t>(prm->n_seqs_bound, prm->n_seqs_global), seqs->n);
+    bool own_lists = false;                                  // index lists were made for this handle (capable / other split)
     for (auto& b : seqs->buckets) {
         if (b.mclass == kLongClass || global_tables) {       // beyond the length classes / tables beyond LDS: long_seq.hip
             EmBucket eb;
@@ -179,16 +180,15 @@ int plan_launches(bamm_em* em, bool global_tables, const uint8_t* seq_mask, Prim
             if (all) { eb.count = b.count; eb.d_idx = b.d_idx; }
             else {
                 uint32_t* d = nullptr;
-                if ((rc = dev_upload(c, &d, yes.data(), yes.size()))) return rc;
-                em->owned_idx.push_back(d);
+                if ((rc = em->mem.upload(&d, yes.data(), yes.size()))) return rc;
+                own_lists = true;
                 eb.count = (uint32_t)yes.size(); eb.d_idx = d;
             }
             if ((glayout & 8u) && eb.count) {
                 // mixed rows: every lane's stream window and fix-lane codes per launch slot of this bucket, derived once
                 // here instead of in every pass (lane_records.h; 512 bytes per sequence, set-sized: from the scratch pool)
                 uint2* rec = nullptr;
-                if ((rc = scratch_alloc(c, &rec, (size_t)eb.count * 64u))) return rc;
-                em->owned_lane_rec.push_back(rec);
+                if ((rc = em->mem.scratch(&rec, (size_t)eb.count * 64u))) return rc;
                 if ((rc = launch_mix_records(eb.mclass, make_view(seqs, em->exc, eb.d_idx, eb.count, nullptr), xr->d_xrec, prm->W,
                                              gg.T, gg.mixB, rec, (uint32_t)std::max(1, c->num_cus), st))) return rc;
                 eb.d_lane_rec = rec;
@@ -201,15 +201,15 @@ int plan_launches(bamm_em* em, bool global_tables, const uint8_t* seq_mask, Prim
         eb.mclass = b.mclass;
         if (!no.empty()) {
             uint32_t* d = nullptr;
-            if ((rc = dev_upload(c, &d, no.data(), no.size()))) return rc;
-            em->owned_idx.push_back(d);
+            if ((rc = em->mem.upload(&d, no.data(), no.size()))) return rc;
+            own_lists = true;
             eb.count = (uint32_t)no.size(); eb.d_idx = d;
         } else { eb.count = b.count; eb.d_idx = b.d_idx; }
         eb.work = (double)eb.count * Mcls;
         em->ebuckets.push_back(eb);
         prime(eb);
     }
-    if (!em->owned_idx.empty() && hipStreamSynchronize(st) != hipSuccess) { set_error("stream sync failed"); return BAMM_ERR_HIP; }
+    if (own_lists && hipStreamSynchronize(st) != hipSuccess) { set_error("stream sync failed"); return BAMM_ERR_HIP; }
     // launch geometry: blocks split over the launches in proportion to their work
     double total_work = 0;
     for (auto& b : em->ebuckets) total_work += b.work;
@@ -270,18 +270,18 @@ int plan_launches(bamm_em* em, bool global_tables, const uint8_t* seq_mask, Prim
                 if (off + need <= end) {
                     em->fusable = true;
                     em->fuse_upd_off = off;
-                    if ((rc = dev_alloc(&em->d_s_block, (size_t)eb.blocks * prm->W * (Y + 1u)))) return rc;
+                    if ((rc = em->mem.alloc(&em->d_s_block, (size_t)eb.blocks * prm->W * (Y + 1u)))) return rc;
                 }
             }
         }
     }
     if (sliced && em->e_fused && c->use_e_list) {
-        if ((rc = scratch_alloc(c, &em->d_list_r, (size_t)seqs->total_len)) || (rc = scratch_alloc(c, &em->d_list_p, (size_t)seqs->total_len)) ||
-            (rc = dev_alloc(&em->d_list_n, (size_t)seqs->n))) return rc;
+        if ((rc = em->mem.scratch(&em->d_list_r, (size_t)seqs->total_len)) || (rc = em->mem.scratch(&em->d_list_p, (size_t)seqs->total_len)) ||
+            (rc = em->mem.alloc(&em->d_list_n, (size_t)seqs->n))) return rc;
         if (hipMemsetAsync(em->d_list_n, 0, (seqs->n ? seqs->n : 1) * sizeof(uint32_t), st) != hipSuccess) { set_error("hipMemsetAsync failed"); return BAMM_ERR_HIP; }
         // lists or dense r, per pass: the first pass of a handle takes the dense flavour (nothing is known yet: the
         // counter starts saturated), later ones lists once fewer than list_threshold_pct of the windows are non-zero
-        if ((rc = dev_alloc(&em->d_nnz, 2))) return rc;
+        if ((rc = em->mem.alloc(&em->d_nnz, 2))) return rc;
         const unsigned long long start[2] = {~0ull, 0ull};
         if (hipMemcpyAsync(em->d_nnz, start, sizeof start, hipMemcpyHostToDevice, st) != hipSuccess) { set_error("hipMemcpyAsync failed"); return BAMM_ERR_HIP; }
         unsigned long long windows = 0;
@@ -293,4 +293,45 @@ int plan_launches(bamm_em* em, bool global_tables, const uint8_t* seq_mask, Prim
     return BAMM_OK;
 }
 
+uint32_t MaskPlan::waves_for(size_t table) const {
+    return wave_global ? 4u : (uint32_t)std::max<size_t>(1, std::min<size_t>(4, (kLds - table) / wave_bytes));
+}
+
+MaskPlan mask_plan(uint32_t W, uint32_t Y, uint32_t max_len, uint64_t n_seqs, size_t cells, int num_cus) {
+    auto round16 = [](size_t x) { return (x + 15) & ~(size_t)15; };
+    const size_t s_bytes = round16((size_t)W * (Y + 1) * sizeof(float));
+    MaskPlan p{};
+    p.direct = round16((size_t)Y * 8) > kLds;
+    p.wave_global = p.direct || mask_wave_bytes(max_len, false) + round16((size_t)Y * 8) > kLds || max_len > 65535u;
+    p.wave_bytes = mask_wave_bytes(max_len, p.wave_global);
+    p.s_in_lds = s_bytes <= 64 * 1024 && (p.wave_global || s_bytes + p.wave_bytes <= kLds);
+    p.e_table = p.s_in_lds ? s_bytes : 0;
+    p.m_cols = p.direct ? W : (uint32_t)std::min<size_t>(W, (p.wave_global ? kLds / 2 : std::min(kLds / 2, kLds - p.wave_bytes)) / ((size_t)Y * 8));
+    p.m_cols = std::max(1u, p.m_cols);
+    p.m_table = p.direct ? 0 : round16((size_t)p.m_cols * Y * 8);
+    p.init_table = (uint32_t)round16((size_t)W * 4 * sizeof(float));
+    p.e_waves = p.waves_for(p.e_table); p.m_waves = p.waves_for(p.m_table);
+    // 16 waves per CU (as the fused kernel), but no more partial tables than 64 MiB worth
+    // (arrays in global memory: at most 2048 waves' worth of them)
+    // ... and no more than 8 GiB of them: a launch has at most cus * 8 blocks of 4 waves
+    p.cus = p.wave_global ? (uint32_t)std::max<size_t>(1, std::min<size_t>(std::min(64u, (uint32_t)std::max(1, num_cus)), ((size_t)8 << 30) / (32 * p.wave_bytes)))
+                          : (uint32_t)std::max(1, num_cus);
+    const uint32_t per_cu = std::max(1u, 16u / std::min(p.e_waves, p.m_waves));
+    const uint32_t cap_blocks = p.direct ? p.cus * 8u        // no partial tables at all
+                                         : (uint32_t)std::max<size_t>(p.cus, std::min<size_t>((size_t)p.cus * per_cu, ((size_t)64 << 20) / (cells * 8)));
+    p.mblocks = std::max(1u, std::min(((uint32_t)n_seqs + std::min(p.e_waves, p.m_waves) - 1) / std::min(p.e_waves, p.m_waves), cap_blocks));
+    // every launch has at most cus * 8 blocks of 4 waves
+    p.wave_scratch_bytes = p.wave_global ? (size_t)std::max(p.cus * 8u, p.mblocks) * 4u * p.wave_bytes : 0;
+    return p;
+}
+
 }  // namespace bamm
+
+extern "C" int bamm_mask_plan(uint32_t W, uint32_t Y, uint32_t max_len, uint64_t n_seqs, uint64_t cells, int num_cus, uint64_t* out) {
+    if (!out || !W || !Y || !cells) { bamm::set_error("bamm_mask_plan: bad argument"); return BAMM_ERR_ARG; }
+    const bamm::MaskPlan p = bamm::mask_plan(W, Y, max_len, n_seqs, (size_t)cells, num_cus);
+    const uint64_t v[13] = {p.direct, p.wave_global, p.wave_bytes, p.s_in_lds, p.e_table, p.m_cols, p.m_table, p.init_table,
+                            p.e_waves, p.m_waves, p.cus, p.mblocks, p.wave_scratch_bytes};
+    std::copy(v, v + 13, out);
+    return BAMM_OK;
+}

@@ -10,7 +10,7 @@ using namespace bamm;
 namespace bamm {
 
 int score_on_device(bamm_ctx* c, bamm_seqs* s, const uint8_t* seq_mask, uint32_t K, uint32_t W, uint32_t bg_order, const float* v,
-                    const float* vbg, bool want_mops, bool pooled_mops, DevTemps& tmp, DeviceScores* out) {
+                    const float* vbg, bool want_mops, bool pooled_mops, DevBlocks& tmp, DeviceScores* out) {
     const uint32_t Y = (uint32_t)ipow4(K + 1), Ys = Y + 1, Kbg = std::min(bg_order, K);
     const uint32_t Yb = (uint32_t)ipow4(Kbg + 1);
     // Motif::calculateLogS (Motif.cpp:471-483) with the host's logf, laid out [j][y] + neutral row
@@ -83,7 +83,7 @@ int bamm_seed_from_pwm(bamm_ctx* c, bamm_seqs* s, uint32_t K, uint32_t W, const 
     int* d_counts = nullptr;
     uint32_t* d_z = nullptr;
     unsigned char* d_wave = nullptr;
-    DevTemps tmp(c);
+    DevBlocks tmp(c);
     if ((rc = tmp.upload(&d_score, score, (size_t)4 * W)) || (rc = tmp.upload(&d_u, u, s->n)) ||
         (rc = tmp.alloc(&d_counts, vsz)) || (z && (rc = tmp.alloc(&d_z, s->n)))) return rc;
     if (hipMemsetAsync(d_counts, 0, vsz * sizeof(int), st) != hipSuccess) { set_error("hipMemsetAsync failed"); return BAMM_ERR_HIP; }
@@ -123,7 +123,7 @@ int bamm_logodds_subset(bamm_ctx* c, bamm_seqs* s, const uint8_t* seq_mask, uint
         for (uint64_t n = 0; n < s->n; n++) windows += s->h_len[n] - W + 1;
         if (mops_cap < windows) { set_error("mops buffer too small"); return BAMM_ERR_ARG; }
     }
-    DevTemps tmp(c);
+    DevBlocks tmp(c);
     DeviceScores d;
     int rc = score_on_device(c, s, seq_mask, K, W, bg_order, v, vbg, mops != nullptr, false, tmp, &d);
     std::vector<uint32_t> hz(s->n);

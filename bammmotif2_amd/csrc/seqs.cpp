@@ -57,15 +57,15 @@ int exceptions_for_order(bamm_seqs* s, uint32_t K, ExcK** out) {
         }
     });
     k.count = k.h_ex.size();
-    int rc = dev_upload(s->ctx, &k.d_off, k.h_off.data(), k.h_off.size());
+    DevBlocks made(s->ctx);                                  // the set's once the table is complete
+    int rc = made.upload(&k.d_off, k.h_off.data(), k.h_off.size());
+    if (!rc) rc = made.upload(&k.d_exc, k.h_ex.data(), k.h_ex.size());
     if (rc) return rc;
-    rc = dev_upload(s->ctx, &k.d_exc, k.h_ex.data(), k.h_ex.size());
-    if (rc) { (void)hipFree(k.d_off); return rc; }
     if (hipStreamSynchronize(s->ctx->stream) != hipSuccess) {
-        (void)hipFree(k.d_off); (void)hipFree(k.d_exc);
         set_error("stream sync failed while uploading the exception list");
         return BAMM_ERR_HIP;
     }
+    s->mem.adopt(made, k.d_off); s->mem.adopt(made, k.d_exc);
     auto ins = s->exc_by_order.emplace(K, std::move(k));
     *out = &ins.first->second;
     return BAMM_OK;
@@ -123,13 +123,14 @@ int xrec_for_group(bamm_seqs* s, uint32_t K, uint32_t G, ExcK* k, const ExcK::XR
         xrec[n] = make_uint4(lo | (B << 12), w3[0], w3[1], w3[2]);
     }
     });
-    int rc = dev_upload(s->ctx, &x.d_xrec, xrec.data(), xrec.size());
+    DevBlocks made(s->ctx);
+    int rc = made.upload(&x.d_xrec, xrec.data(), xrec.size());
     if (rc) return rc;
     if (hipStreamSynchronize(s->ctx->stream) != hipSuccess) {
-        (void)hipFree(x.d_xrec);
         set_error("stream sync failed while uploading the sequence records");
         return BAMM_ERR_HIP;
     }
+    s->mem.adopt(made, x.d_xrec);
     auto ins = k->xrec.emplace(G, std::move(x));
     *out = &ins.first->second;
     return BAMM_OK;
@@ -141,19 +142,18 @@ using namespace bamm;
 
 extern "C" {
 
-// device arrays of a whole packed set that its maker already holds (bamm_seqs_from_codes): the resident set takes them over
-// instead of uploading the host copies again.  A pointer the set has taken is nulled here; the caller frees what is left.
-struct AdoptDev { uint32_t* words; uint64_t* word_off; uint32_t* len; uint64_t* pos_off; };   // words: 80 words of slack behind the stream
+// device arrays of a whole packed set that its maker already holds in `owner` (bamm_seqs_from_codes): the resident set adopts
+// them instead of uploading the host copies again
+struct AdoptDev { DevBlocks* owner; uint32_t* words; uint64_t* word_off; uint32_t* len; uint64_t* pos_off; };   // words: 80 words of slack behind the stream
 
-static int seqs_upload_impl(bamm_ctx* c, const bamm_packed* p, uint64_t begin, uint64_t end, bamm_seqs** out, AdoptDev* have) {
+static int seqs_upload_impl(bamm_ctx* c, const bamm_packed* p, uint64_t begin, uint64_t end, bamm_seqs** out, const AdoptDev* have) {
     if (!c || !p || !out || begin > end || end > p->n_seqs) {
         set_error("bamm_seqs_upload: bad argument");
         return BAMM_ERR_ARG;
     }
     if (end - begin > 0xfffffff0ull) { set_error("more than 2^32 sequences per device"); return BAMM_ERR_UNSUPPORTED; }
     BAMM_HIP(hipSetDevice(c->device));
-    std::unique_ptr<bamm_seqs> s(new bamm_seqs());
-    s->ctx = c;
+    std::unique_ptr<bamm_seqs> s(new bamm_seqs(c));
     s->n = end - begin;
     const uint64_t w0 = p->word_off[begin], w1 = p->word_off[end];
     std::vector<uint64_t> woff(s->n + 1);
@@ -192,15 +192,15 @@ static int seqs_upload_impl(bamm_ctx* c, const bamm_packed* p, uint64_t begin, u
     // 80 zero words of slack: the grouped kernel reads a lane's words without checking the sequence's end
     if (have && begin == 0 && end == p->n_seqs) {
         s->d_words = have->words; s->d_word_off = have->word_off; s->d_len = have->len; s->d_pos_off = have->pos_off;
-        have->words = nullptr; have->word_off = nullptr; have->len = nullptr; have->pos_off = nullptr;   // the set's from here on
+        for (void* q : {(void*)s->d_words, (void*)s->d_word_off, (void*)s->d_len, (void*)s->d_pos_off}) s->mem.adopt(*have->owner, q);
         BAMM_HIP(hipMemsetAsync(s->d_words + (w1 - w0), 0, 80 * sizeof(uint32_t), c->stream));
     } else {
-        if ((rc = dev_alloc(&s->d_words, (w1 - w0) + 80))) return rc;
+        if ((rc = s->mem.alloc(&s->d_words, (w1 - w0) + 80))) return rc;
         BAMM_HIP(hipMemsetAsync(s->d_words + (w1 - w0), 0, 80 * sizeof(uint32_t), c->stream));
         if ((rc = ctx_upload(c, s->d_words, p->words + w0, (w1 - w0) * sizeof(uint32_t)))) return rc;
-        if ((rc = dev_upload(c, &s->d_word_off, woff.data(), woff.size()))) return rc;
-        if ((rc = dev_upload(c, &s->d_len, s->h_len.data(), s->h_len.size()))) return rc;
-        if ((rc = dev_upload(c, &s->d_pos_off, s->h_pos_off.data(), s->h_pos_off.size()))) return rc;
+        if ((rc = s->mem.upload(&s->d_word_off, woff.data(), woff.size()))) return rc;
+        if ((rc = s->mem.upload(&s->d_len, s->h_len.data(), s->h_len.size()))) return rc;
+        if ((rc = s->mem.upload(&s->d_pos_off, s->h_pos_off.data(), s->h_pos_off.size()))) return rc;
     }
     int used = 0;
     for (int mc = 0; mc <= kNumMClasses; mc++) used += !members[mc].empty();
@@ -213,7 +213,7 @@ static int seqs_upload_impl(bamm_ctx* c, const bamm_packed* p, uint64_t begin, u
         else for (uint32_t n : members[mc]) b.work += s->h_len[n] / 8.0;   // ~8x the cost per position of the fast kernels
         s->buckets.push_back(b);
         if (used > 1) {
-            if ((rc = dev_upload(c, &s->buckets.back().d_idx, members[mc].data(), members[mc].size()))) return rc;
+            if ((rc = s->mem.upload(&s->buckets.back().d_idx, members[mc].data(), members[mc].size()))) return rc;
             s->buckets.back().h_idx = std::move(members[mc]);
         }
     }
@@ -245,7 +245,7 @@ int bamm_seqs_from_codes(bamm_ctx* c, const uint8_t* codes, const uint64_t* off,
     BAMM_HIP(hipSetDevice(c->device));
     hipStream_t st = c->stream;
     const uint64_t n_codes = off[n_seqs] - off[0];
-    DevTemps tmp(c);                                         // everything allocated here is freed on every path out
+    DevBlocks tmp(c);                                        // everything allocated here is freed on every path out
     int rc;
     uint8_t* d_codes = nullptr;
     uint64_t* d_off = nullptr;
@@ -320,11 +320,8 @@ int bamm_seqs_from_codes(bamm_ctx* c, const uint8_t* codes, const uint64_t* off,
     p->max_len = mx; p->min_len = mn;
     if (seqs_out) {
         // the stream, its offsets and the lengths are on the device already: the resident set takes those arrays over
-        AdoptDev have{a.words, a.word_off, a.len, a.pos_off};
-        rc = seqs_upload_impl(c, p, 0, n_seqs, seqs_out, &have);
-        for (void* taken : {(void*)a.words, (void*)a.word_off, (void*)a.len, (void*)a.pos_off})
-            if (taken != have.words && taken != have.word_off && taken != have.len && taken != have.pos_off) tmp.keep(taken);
-        if (rc) { bamm_packed_free(p); return rc; }
+        const AdoptDev have{&tmp, a.words, a.word_off, a.len, a.pos_off};
+        if ((rc = seqs_upload_impl(c, p, 0, n_seqs, seqs_out, &have))) { bamm_packed_free(p); return rc; }
     }
     *packed_out = p;
     return BAMM_OK;
@@ -341,7 +338,7 @@ int bamm_seqs_bg_model(bamm_ctx* c, bamm_seqs* s, uint32_t K, const float* alpha
         ExcK* exc = nullptr;
         int rc = exceptions_for_order(s, K, &exc);
         if (rc) return rc;
-        DevTemps tmp(c);
+        DevBlocks tmp(c);
         unsigned long long* d_counts = nullptr;
         if ((rc = tmp.alloc(&d_counts, Y))) return rc;
         hipError_t e = hipMemsetAsync(d_counts, 0, Y * sizeof(unsigned long long), c->stream);
@@ -377,7 +374,7 @@ int bamm_sample_negatives(bamm_ctx* c, bamm_seqs* pos, uint32_t s_order, uint64_
     ExcK* exc = nullptr;
     int rc = exceptions_for_order(pos, s_order, &exc);
     if (rc) return rc;
-    DevTemps tmp(c);
+    DevBlocks tmp(c);
     NegArgs a{};
     a.words = pos->d_words; a.word_off = pos->d_word_off; a.len = pos->d_len; a.exc_off = exc->d_off; a.exc = exc->d_exc;
     a.n = pos->n; a.s = s_order; a.generic = generic; a.m_fold = m_fold; a.keep_stride = keep_stride;

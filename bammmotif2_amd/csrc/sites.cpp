@@ -44,7 +44,7 @@ int bamm_em_sites(bamm_em* em, uint64_t begin, uint64_t end, float cutoff, bamm_
     hipStream_t st = c->stream;
     int rc;
 
-    DevTemps tmp(c);
+    DevBlocks tmp(c);
     uint32_t *d_count = nullptr, *d_z = nullptr;
     float* d_best = nullptr;
     unsigned long long *d_offset = nullptr, *d_total = nullptr;
@@ -62,7 +62,7 @@ int bamm_em_sites(bamm_em* em, uint64_t begin, uint64_t end, float cutoff, bamm_
         uint64_t ce = cb + 1;
         if (resident_r) ce = end;
         else while (ce < end && s->h_pos_off[ce + 1] - s->h_pos_off[cb] <= budget) ce++;
-        DevTemps chunk_tmp(c);                               // the chunk's r and its records go back to the pool behind it
+        DevBlocks chunk_tmp(c);                              // the chunk's r and its records go back to the pool behind it
         DenseR dr;
         if ((rc = dense_r_on_device(em, cb, ce, chunk_tmp, &dr))) return rc;
         SitesArgs a{};

@@ -147,6 +147,22 @@ def device_count() -> int:
     return int(n.value)
 
 
+def device_blocks_live() -> int:
+    """Device blocks the library has handed out and not yet taken back, process-wide (bamm_device_blocks_live; for tests)."""
+    return int(abi.load().bamm_device_blocks_live())
+
+
+MASK_PLAN_FIELDS = ("direct", "wave_global", "wave_bytes", "s_in_lds", "e_table", "m_cols", "m_table", "init_table", "e_waves",
+                    "m_waves", "cus", "mblocks", "wave_scratch_bytes")
+
+
+def mask_plan(W: int, Y: int, max_len: int, n_seqs: int, cells: int, num_cus: int) -> dict:
+    """The launch geometry of EM.mask() for these sizes (bamm_mask_plan: a pure function, no device needed)."""
+    out = np.zeros(len(MASK_PLAN_FIELDS), np.uint64)
+    check(abi.load().bamm_mask_plan(W, Y, max_len, n_seqs, cells, num_cus, out))
+    return dict(zip(MASK_PLAN_FIELDS, (int(x) for x in out)))
+
+
 def device_pci_bus_id(device: int) -> str:
     buf = C.create_string_buffer(32)
     check(abi.load().bamm_device_pci_bus_id(int(device), buf, 32))

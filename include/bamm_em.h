@@ -148,6 +148,10 @@ int  bamm_ctx_set_launch(bamm_ctx* ctx, uint32_t blocks, uint32_t threads_per_bl
  *                       sequences; 0 = the default, 2^27 positions = 512 MiB); read at the call, not at handle creation
  * There are no environment variables that change what the library computes or launches.          */
 int  bamm_ctx_set_tuning(bamm_ctx* ctx, const char* key, int value);
+/* Device blocks the library has handed to an owner (a sequence set, a handle, a call's temporaries) and not yet taken
+ * back, over the whole process; blocks that wait idle in a context's scratch pool are not counted.  For the tests' check
+ * that destroying a handle returns all it allocated -- nothing else reads it.                                     */
+long long bamm_device_blocks_live(void);
 
 /* ------------------------------------------------------------------ sequences ----------- */
 /* Uploads sequences [begin,end) of `p`; they stay resident and are shared (ref-counted) by
@@ -365,6 +369,11 @@ int  bamm_em_plan_mixed(bamm_em* em, uint64_t* mixed_seqs);
  * reference's layout), 0 when it is sliced as well (r per position slot); *long_seqs = sequences beyond
  * BAMM_MAX_SEQ_POSITIONS, which go window by window (long_seq.hip).  Any pointer may be NULL.               */
 int  bamm_em_plan_paths(bamm_em* em, int* sliced, int* e_fused, uint64_t* long_seqs);
+/* The launch geometry bamm_em_mask computes for a model of width W with Y = 4^(K+1) rows (cells = W * Y) on a set of
+ * n_seqs sequences, the longest of max_len positions, on a device of num_cus CUs -- a pure function, exported for tests
+ * (no device needed).  out[13]: direct, wave_global, wave_bytes, s_in_lds, e_table, m_cols, m_table, init_table, e_waves,
+ * m_waves, cus, mblocks, wave_scratch_bytes (csrc/handles.h: MaskPlan).                                           */
+int  bamm_mask_plan(uint32_t W, uint32_t Y, uint32_t max_len, uint64_t n_seqs, uint64_t cells, int num_cus, uint64_t* out);
 
 /* ------------------------------------------------------------------ seeding ------------- */
 /* The pass over the sequences of Motif::initFromPWM (Motif.cpp:228-311): 0th-order posterior of
