@@ -257,13 +257,17 @@ int launch_em_grp_xl(int mclass, bool accum, bool write_r, const GrpKernelArgs& 
 uint32_t grp_max_threads(int M);   // block size the grouped kernel of this length class is built for
 // mixed rows: geometry (false: does not apply / does not fit) and the launchers of its two translation units
 bool mix_geometry(uint32_t K, uint32_t W, int M, uint32_t waves, bool accum, GrpGeom* out);
+// mixed rows, accumulating layout: the motif's leading columns whose bins [j][y] are resident in LDS (K = 2: 64 bins of 8 bytes);
+// the fix lanes add to those and log the other columns' sums -- the kernel and the builder of the lane records agree through this
+inline __host__ __device__ uint32_t mix_resident_cols(const GrpGeom& g) { return g.wave_bytes / (64u * 8u); }
 int launch_em_mix(int mclass, bool accum, bool write_r, const GrpKernelArgs& a, uint32_t blocks, uint32_t threads, hipStream_t st);
 int launch_em_mix1(int mclass, bool accum, bool write_r, const GrpKernelArgs& a, uint32_t blocks, uint32_t threads, hipStream_t st);
 int launch_em_grp(int mclass, bool accum, bool write_r, const GrpKernelArgs& a, uint32_t blocks, uint32_t threads,
                   hipStream_t st);
-// lane_records.hip: the lane records of one mixed-row bucket (sv: its launch slots; T groups, the first B narrow) into
-// out[sv.count][64]; num_cus == kPrimeOnly loads the builder's code object and launches nothing
-int launch_mix_records(int mclass, const SeqView& sv, const uint4* xrec, uint32_t W, uint32_t T, uint32_t B, uint2* out,
+// lane_records.hip: the lane records of one mixed-row bucket (sv: its launch slots; T groups, the first B narrow; the
+// accumulating layout keeps bins of the motif's first n1c columns resident) into out[sv.count][64]; num_cus == kPrimeOnly
+// loads the builder's code object and launches nothing
+int launch_mix_records(int mclass, const SeqView& sv, const uint4* xrec, uint32_t W, uint32_t T, uint32_t B, uint32_t n1c, uint2* out,
                        uint32_t num_cus, hipStream_t st);
 
 struct SeedKernelArgs {          // Motif::initFromPWM's pass over the sequences (seed.hip)

@@ -29,6 +29,27 @@
 namespace bamm {
 namespace {
 
+// one 7-bit field of a lane record's word y as ONE instruction whose result stays in its register for both of its uses (left to
+// itself the compiler folds the extract into each use's own shift and mask: three instructions per column where two do)
+__device__ __forceinline__ uint32_t field7(uint32_t w, int at) {
+    uint32_t f;
+    asm("v_bfe_u32 %0, %1, %2, 7" : "=v"(f) : "v"(w), "n"(at));
+    return f;
+}
+
+// The rows of one slot in the two tables.  `special` is 0 for a slot that takes its rows from the stream window -- the 6-mer
+// that ends at bit `at` of X and the 5-mer in its low ten bits -- and else the slot's row in the 6-mer table: the neutral row
+// (4096) or a virtual one behind it; the 5-mer table has the same rows kMixRow5Bias = 4096 - 1024 lower.  A special row is above
+// every stream row, so each table's row is one maximum instead of a compare and two selects; the 5-mer row comes out
+// kMixRow5Bias too high for stream and special rows alike (the 6-mer's two high bits set: one OR of the shared extract), which
+// the two base addresses it is scaled onto take back.
+constexpr uint32_t kMixRow5Bias = 3072u;
+__device__ __forceinline__ void mix_rows(uint32_t X, int at, uint32_t special, uint32_t& row5_biased, uint32_t& row6) {
+    const uint32_t six = (X >> at) & 4095u;
+    row6 = max(six, special);
+    row5_biased = max(six | kMixRow5Bias, special);
+}
+
 template <int OFF>
 __device__ __forceinline__ void lds_add_u64_exec_big(uint32_t byte_addr, unsigned long long v, unsigned long long mask) {
     static_assert(OFF >= 0 && OFF < 65536, "ds offset field");
@@ -67,7 +88,7 @@ __global__ void __launch_bounds__(THREADS) k_em_mix(GrpKernelArgs ga) {
     // for those columns is added here; only the other columns' sums go through the log (each logged entry costs a
     // store request in the loop and a read in the epilogue: all of them 0.875 ms, a third of them 0.814 ms)
     unsigned long long* n1p = reinterpret_cast<unsigned long long*>(lds_raw + g.off_wave);
-    const uint32_t n1c = ACCUM ? g.wave_bytes / (Y * 8u) : 0u;
+    const uint32_t n1c = ACCUM ? mix_resident_cols(g) : 0u;
 
     const int lane = threadIdx.x & 63;
     const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -148,16 +169,35 @@ __global__ void __launch_bounds__(THREADS) k_em_mix(GrpKernelArgs ga) {
     const float one_minus_q = 1.0f - q;
     const uint32_t lane_b = (uint32_t)lane / T, lane_t = (uint32_t)lane - lane_b * T;     // fix-lane roles: (row, group)
     const bool lane_wide = lane_t >= B;
-    const uint32_t lane_col0 = lane_wide ? 3u * B + 4u * (lane_t - B) : 3u * lane_t;
+    const uint32_t lane_col0 = mix_group_col0(lane_t, B);
     const uint32_t vbase5 = R5V0 + wave * kMixBv, vbase6 = R6V0 + wave * kMixBv;
-    const uint32_t sg5_base = lds_offset(sg5), sg6_base = lds_offset(sg6);
+    const uint32_t sg6_base = lds_offset(sg6);
+    const uint32_t sg5_base_biased = lds_offset(sg5) - kMixRow5Bias * (rs5 * 4u);   // for rows kMixRow5Bias too high (mix_rows; mod 2^32)
 
-    // per lane, fixed for the launch: bit 6 (the value Y) of every 7-bit field of `yfix` whose column has a resident bin -- OR-ed
-    // into the sequence's codes it marks those columns "nothing to log" in one instruction
-    uint32_t resident_fill = 0u;
+    // per lane, fixed for the launch: bit 6 (the value Y) of every 7-bit field of `yfix` whose column has a resident bin (OR-ed
+    // into the sequence's codes it marks those columns "nothing to log"), shifted to where the log's code word has its
+    // fields, next to the lane's group -- the code word is one shift-and-OR of the record's word
+    const uint32_t resident_fill = mix_resident_fill(lane_col0, n1c);
+    [[maybe_unused]] uint32_t code_fill = lane_t | (resident_fill << 3);
+    asm volatile("" : "+v"(code_fill));                      // opaque: the compiler does not take the constant apart again (OR, then shift-and-OR)
+    // a fourth column has a resident bin only in a wide group (a narrow lane's fourth field is always Y): with none
+    // among the resident columns -- W = 20: 11 of them, all narrow -- the fourth predicated add is not issued at all
+    [[maybe_unused]] const bool resident_wide = __builtin_amdgcn_readfirstlane((uint32_t)(n1c > 3u * B + 3u)) != 0u;
+    // per column, fixed for the launch: the lanes whose column has a resident bin, as a mask for the scalar unit (opaque: kept
+    // as the 64 bits it is, not turned back into a per-lane flag and compared again in every sequence)
+    [[maybe_unused]] unsigned long long resident_lanes[4];
 #pragma unroll
-    for (int c = 0; c < 4; c++)
-        if (lane_col0 + (uint32_t)c < n1c) resident_fill |= Y << (7 * c);
+    for (int c = 0; c < 4; c++) {
+        resident_lanes[c] = __builtin_amdgcn_ballot_w64(((resident_fill >> (7 * c + 6)) & 1u) != 0u);
+        asm volatile("" : "+s"(resident_lanes[c]));
+    }
+    // byte offset of the lane's first column in the single-column table [W][Y+1] and LDS address of its first column's
+    // resident bins; the other columns follow at constant distances, which the instructions' offset fields take.  (A narrow
+    // lane's fourth column is the next group's first: within the motif, a wide group follows; its field is always Y.)
+    const uint32_t fix_s1 = __umul24(lane_col0, Ys * 4u);
+    // the lane's virtual odds cell, in whichever table its group is: one address, one write per sequence for narrow and wide lanes alike
+    float* const fix_odds = lane_wide ? sg6 + ((vbase6 + lane_b) * A + (lane_t - B)) : sg5 + (__umul24(vbase5 + lane_b, rs5) + pad + lane_t);
+    [[maybe_unused]] const uint32_t fix_bin = lds_offset(n1p) + lane_col0 * (Y * 8u);
     double llh_acc = 0.0, sumr_acc = 0.0;
     uint32_t seq_cnt = 0, last_LW1 = 0;
     float pos_i = 0.0f;
@@ -168,7 +208,7 @@ __global__ void __launch_bounds__(THREADS) k_em_mix(GrpKernelArgs ga) {
 #pragma unroll
     for (int m = 0; m < M; m++) pos_m[m] = 0.0f;
 #pragma unroll
-    for (int m = 0; m < (kCacheSpec ? M : 1); m++) spec[m] = -1;
+    for (int m = 0; m < (kCacheSpec ? M : 1); m++) spec[m] = 0;
     [[maybe_unused]] GrpLogEntry* my_log = nullptr;          // the fix lanes' non-zero sums (8-byte entries)
     [[maybe_unused]] uint32_t nlog = 0;
     if constexpr (ACCUM)
@@ -204,20 +244,23 @@ __global__ void __launch_bounds__(THREADS) k_em_mix(GrpKernelArgs ga) {
         // LW1 .. LW1+2 whose groups are cut by the edge.  The fix lanes' reads of the single-column table are issued
         // first and waited for after the rows of all positions are decoded: the wave is not yet bound by the LDS pipe
         // here, the round trip is latency it would otherwise sit out.
-        const uint32_t X = cur.rec.x, yfix = cur.rec.y;      // the flag stays in: every use extracts fields or shifts it out
-        const bool fix = (int)yfix < 0;                      // kMixFixBit, the sign: one compare
+        const uint32_t X = cur.rec.x, yfix = cur.rec.y;      // the flags stay in: every use extracts fields or shifts them out
+        const bool fix = (int)X < 0;                         // kMixFixBit, the sign: one compare
         const uint32_t xw = __builtin_amdgcn_readfirstlane(cur.xw);
         const uint32_t Bx = (xw >> 12) & 0xfu;
         const uint32_t xlo = xw & 0xfffu;
         const uint32_t nE = min(kMixNe, L - LW1);
-        float fs[4] = {1.0f, 1.0f, 1.0f, 1.0f};
-        const float* const sfix_now = (ACCUM && kp->fused) ? kp->s_block + (size_t)blockIdx.x * (W * Ys) : kp->e.s;
-        if (fix) {
+        float fs[4];                                         // a fix lane's column odds; no other lane reads them
+        uint32_t yf[4];                                      // the columns' codes, extracted once for both uses
 #pragma unroll
-            for (int c = 0; c < 4; c++) {
-                const uint32_t colc = min(lane_col0 + (uint32_t)c, W - 1u);
-                fs[c] = sfix_now[__umul24(colc, Ys) + ((yfix >> (7 * c)) & 0x7fu)];    // global, through L1 / L2
-            }
+        for (int c = 0; c < 4; c++) yf[c] = field7(yfix, 7 * c);
+        const char* const sfix_now = reinterpret_cast<const char*>((ACCUM && kp->fused) ? kp->s_block + (size_t)blockIdx.x * (W * Ys) : kp->e.s);
+        if (fix) {
+            // a 32-bit byte offset beside the uniform base: the load takes the base from SGPRs, the lane pays one extract
+            // and one shift-and-add per column (no 64-bit address arithmetic)
+#pragma unroll
+            for (int c = 0; c < 4; c++)
+                fs[c] = *reinterpret_cast<const float*>(sfix_now + ((yf[c] << 2) + fix_s1) + c * (int)(Ys * 4u));    // global, through L1 / L2
         }
         // Which slots do not take their row from the stream -- beyond the EM.cpp:167 edge (neutral row), a
         // virtual row -- depends on (L, the record's first word) only, and sets of one length with the strand
@@ -229,37 +272,29 @@ __global__ void __launch_bounds__(THREADS) k_em_mix(GrpKernelArgs ga) {
 #pragma unroll
             for (int m = 0; m < M; m++) {
                 const uint32_t k2 = p0 + m - xlo, k3 = p0 + m - LW1;
-                o[m] = (p0 + m < LW1) ? -1 : 0;                                          // EM.cpp:167
-                if (k2 < Bx) o[m] = (int)(1u + wave * kMixBv + k2);
-                if (k3 < nE) o[m] = (int)(1u + wave * kMixBv + kMixBj + k3);
+                o[m] = (p0 + m < LW1) ? 0 : (int)R6N;                                    // EM.cpp:167
+                if (k2 < Bx) o[m] = (int)(R6N + 1u + wave * kMixBv + k2);
+                if (k3 < nE) o[m] = (int)(R6N + 1u + wave * kMixBv + kMixBj + k3);
             }
         };
-        uint32_t row5[M], row6[M];
+        static_assert(R6N - R5N == kMixRow5Bias && R5N == 1024u && R6N == 4096u, "mix_rows");
+        uint32_t row5[M], row6[M];                           // row5: kMixRow5Bias too high (mix_rows)
         if constexpr (kCacheSpec) {
             if (LW1 != spec_LW1 || xw != spec_xw) {
                 spec_LW1 = LW1; spec_xw = xw;
                 slot_offsets(spec);
             }
 #pragma unroll
-            for (int m = 0; m < M; m++) {
-                const bool stream = spec[m] < 0;
-                row5[m] = stream ? ((X >> (2 * (M - 1 - m))) & 1023u) : R5N + (uint32_t)spec[m];
-                row6[m] = stream ? ((X >> (2 * (M - 1 - m))) & 4095u) : R6N + (uint32_t)spec[m];
-            }
+            for (int m = 0; m < M; m++) mix_rows(X, 2 * (M - 1 - m), (uint32_t)spec[m], row5[m], row6[m]);
         } else {
             int o[M];
             slot_offsets(o);
 #pragma unroll
-            for (int m = 0; m < M; m++) {
-                const bool stream = o[m] < 0;
-                row5[m] = stream ? ((X >> (2 * (M - 1 - m))) & 1023u) : R5N + (uint32_t)o[m];
-                row6[m] = stream ? ((X >> (2 * (M - 1 - m))) & 4095u) : R6N + (uint32_t)o[m];
-            }
+            for (int m = 0; m < M; m++) mix_rows(X, 2 * (M - 1 - m), (uint32_t)o[m], row5[m], row6[m]);
         }
         if (fix) {
             const float f = ((fs[0] * fs[1]) * fs[2]) * fs[3];                         // column order; a neutral entry is 1.0f
-            if (lane_wide) sg6[(vbase6 + lane_b) * A + (lane_t - B)] = f;
-            else sg5[__umul24(vbase5 + lane_b, rs5) + pad + lane_t] = f;
+            *fix_odds = f;
         }
         wave_lds_sync();
 
@@ -269,7 +304,7 @@ __global__ void __launch_bounds__(THREADS) k_em_mix(GrpKernelArgs ga) {
         {
             uint32_t ra[M];
 #pragma unroll
-            for (int m = 0; m < M; m++) ra[m] = sg5_base + __umul24(row5[m], rs5 * 4u);        // v_mad_u32_u24: full rate
+            for (int m = 0; m < M; m++) ra[m] = sg5_base_biased + __umul24(row5[m], rs5 * 4u);   // v_mad_u32_u24: full rate
             // the wide groups' odds are on their way while the narrow groups are chained (one round trip, not two)
             float2 pr[M];
 #pragma unroll
@@ -343,7 +378,7 @@ __global__ void __launch_bounds__(THREADS) k_em_mix(GrpKernelArgs ga) {
                 F[m] = to_fixed40_pre(U[m]);
                 nz[m] = __ballot(F[m] != 0ull);
                 rad6[m] = c6 + row6[m] * 8u;
-                rad5[m] = c5 + row5[m] * 8u;
+                rad5[m] = c5 - kMixRow5Bias * 8u + row5[m] * 8u;                 // (mod 2^32: the bias goes out again)
             }
             // F is a ring: logical slot m lives in F[(m + off) mod M]; a step of G moves the G slots that arrive
             // from the next lane in place (one DPP pair each) and their non-zero masks with them
@@ -387,19 +422,19 @@ __global__ void __launch_bounds__(THREADS) k_em_mix(GrpKernelArgs ga) {
             // code: group (3 bits), then the y of its up to four columns (7 bits each, >= Y = nothing to log: neutral,
             // beyond the edge, or a resident bin, which takes the sum here)
             // (fields of columns beyond the lane's group hold Y already: yfix is built that way)
-            if (acc != 0ull) {
-#pragma unroll
-                for (int c = 0; c < 4; c++) {
-                    const uint32_t yc = (yfix >> (7 * c)) & 0x7fu;
-                    if (yc < Y && ((resident_fill >> (7 * c + 6)) & 1u) != 0u)   // a resident bin: added here, not logged
-                        atomicAdd(&n1p[(lane_col0 + (uint32_t)c) * Y + yc], acc);
-                }
-            }
-            const uint32_t ylog = yfix | resident_fill;          // what is left to log: fields still below Y
-            const uint32_t code = lane_t | (ylog << 3);          // (the record's fix-lane flag, bit 31, falls off here)
-            if ((~ylog & (Y | (Y << 7) | (Y << 14) | (Y << 21))) == 0u) acc = 0ull;   // nothing left to log (also: a group wholly beyond the edge)
-            const unsigned long long nzm = __ballot(acc != 0ull);
-            if (acc != 0ull) {
+            // a column with a y and a resident bin: added here, not logged.  The lanes that add, as masks: every term is one compare's result or fixed for the launch, combined by the scalar unit
+            const unsigned long long has_acc = __builtin_amdgcn_ballot_w64(acc != 0ull);
+            static_for<4>([&](auto cc) {
+                constexpr int c = decltype(cc)::value;
+                if (c == 3 && !resident_wide) return;                            // wave-uniform: no lane has a fourth resident column
+                lds_add_u64_exec<c * (int)(Y * 8u)>(fix_bin + (yf[c] << 3), acc, has_acc & resident_lanes[c] & __builtin_amdgcn_ballot_w64(yf[c] < Y));
+            });
+            // what is left to log: fields still below Y once the resident columns' are filled -- whether there is any
+            // (none also: a group wholly beyond the edge) is the sign of the record's word
+            const uint32_t code = code_fill | (yfix << 3);       // (the flag, bit 31, falls off here)
+            const bool to_log = acc != 0ull && (int)yfix < 0;    // kMixLogBit
+            const unsigned long long nzm = has_acc & __builtin_amdgcn_ballot_w64((int)yfix < 0);
+            if (to_log) {
                 const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(nzm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)nzm, 0u));
                 GrpLogEntry* const log_now = reinterpret_cast<GrpLogEntry*>(kp->fix_log) + (size_t)(blockIdx.x * WAVES + wave) * kp->fix_log_cap;
                 grp_log_store(log_now, nlog + rank, acc, code);

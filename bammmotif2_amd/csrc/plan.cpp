@@ -30,7 +30,7 @@ int prime_bucket(bamm_ctx* c, const bamm_em_params& prm, uint32_t Y, bool sliced
     ga.e = a;
     if (!grp_geometry(prm.K, prm.W, eb.G, kMClasses[eb.mclass], threads / 64u, true, eb.logc, eb.layout, &ga.g)) return BAMM_OK;   // (the launch reports it)
     if (eb.layout & 8u)                                      // mixed rows: the builder of the lane records is the handle's first launch
-        if (int rc = launch_mix_records(eb.mclass, SeqView{}, nullptr, prm.W, ga.g.T, ga.g.mixB, nullptr, kPrimeOnly, c->stream)) return rc;
+        if (int rc = launch_mix_records(eb.mclass, SeqView{}, nullptr, prm.W, ga.g.T, ga.g.mixB, 0u, nullptr, kPrimeOnly, c->stream)) return rc;
     return launch_em_grp(eb.mclass, true, false, ga, kPrimeOnly, threads, c->stream);
 }
 
@@ -186,11 +186,12 @@ int plan_launches(bamm_em* em, bool global_tables, const uint8_t* seq_mask, Prim
             }
             if ((glayout & 8u) && eb.count) {
                 // mixed rows: every lane's stream window and fix-lane codes per launch slot of this bucket, derived once
-                // here instead of in every pass (lane_records.h; 512 bytes per sequence, set-sized: from the scratch pool)
+                // here instead of in every pass (lane_records.h; 512 bytes per sequence, set-sized: from the scratch pool);
+                // gg is the accumulating layout: its resident columns decide what a fix lane has left to log
                 uint2* rec = nullptr;
                 if ((rc = em->mem.scratch(&rec, (size_t)eb.count * 64u))) return rc;
                 if ((rc = launch_mix_records(eb.mclass, make_view(seqs, em->exc, eb.d_idx, eb.count, nullptr), xr->d_xrec, prm->W,
-                                             gg.T, gg.mixB, rec, (uint32_t)std::max(1, c->num_cus), st))) return rc;
+                                             gg.T, gg.mixB, mix_resident_cols(gg), rec, (uint32_t)std::max(1, c->num_cus), st))) return rc;
                 eb.d_lane_rec = rec;
             }
             eb.work = (double)eb.count * Mcls * 0.6;       // grouped passes cost about 60 % per sequence

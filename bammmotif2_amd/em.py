@@ -163,6 +163,21 @@ def mask_plan(W: int, Y: int, max_len: int, n_seqs: int, cells: int, num_cus: in
     return dict(zip(MASK_PLAN_FIELDS, (int(x) for x in out)))
 
 
+def mix_layout(W: int, M: int) -> dict:
+    """The mixed-row kernel's layout for motif width W at M positions per lane (bamm_mix_layout: a pure function, no device
+    needed): T groups of which the first B are narrow and A wide, n1c leading columns with resident bins."""
+    out = (C.c_uint32 * 4)()
+    check(abi.load().bamm_mix_layout(W, M, out))
+    return dict(zip(("T", "B", "A", "n1c"), (int(x) for x in out)))
+
+
+def mix_fix_word(lane: int, W: int, T: int, B: int, n1c: int, L: int, xw: int, xfields: int, sE: int):
+    """(word y of the lane's record, the lane is a fix lane) for one sequence (bamm_mix_fix_word: a pure function, no device needed)."""
+    out = (C.c_uint32 * 2)()
+    check(abi.load().bamm_mix_fix_word(lane, W, T, B, n1c, L, xw, xfields, sE, out))
+    return int(out[0]), bool(out[1])
+
+
 def device_pci_bus_id(device: int) -> str:
     buf = C.create_string_buffer(32)
     check(abi.load().bamm_device_pci_bus_id(int(device), buf, 32))

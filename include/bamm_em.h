@@ -375,6 +375,18 @@ int  bamm_em_plan_paths(bamm_em* em, int* sliced, int* e_fused, uint64_t* long_s
  * m_waves, cus, mblocks, wave_scratch_bytes (csrc/handles.h: MaskPlan).                                           */
 int  bamm_mask_plan(uint32_t W, uint32_t Y, uint32_t max_len, uint64_t n_seqs, uint64_t cells, int num_cus, uint64_t* out);
 
+/* The mixed-row kernel's layout at K = 2 for motif width W and M positions per lane, and one lane's fix-lane word of the lane
+ * records its handles build (csrc/lane_records.h) -- pure functions, exported for tests (no device needed).
+ * bamm_mix_layout: out[4] = T groups, of which the first B are narrow, A wide, n1c leading columns with resident bins in
+ * the accumulating pass; BAMM_ERR_UNSUPPORTED where the mixed rows do not apply.
+ * bamm_mix_fix_word: lane 0..63 of a sequence of L positions; xw = the first word of its group record (lo | B << 12);
+ * xfields = the exact y, 7 bits each, of the four positions that end at the lane's junction row; sE = the 2-bit stream
+ * window that ends at position L - W.  out[2] = the record's word y (four 7-bit column codes, 64 = none; bit 31 =
+ * something is left to log), 1 if the lane is a fix lane of the sequence.                                          */
+int  bamm_mix_layout(uint32_t W, int M, uint32_t* out);
+int  bamm_mix_fix_word(uint32_t lane, uint32_t W, uint32_t T, uint32_t B, uint32_t n1c, uint32_t L, uint32_t xw, uint32_t xfields,
+                       uint32_t sE, uint32_t* out);
+
 /* ------------------------------------------------------------------ seeding ------------- */
 /* The pass over the sequences of Motif::initFromPWM (Motif.cpp:228-311): 0th-order posterior of
  * every window, one motif start sampled per sequence, integer k-mer counts of the sampled sites
