@@ -296,6 +296,20 @@ struct ScoreKernelArgs {
     uint32_t* z;                 // [N]
 };
 
+// ---- long sequences through the register-resident scorer, tile by tile (score_tile.hip) ----
+struct ScoreTileArgs {
+    ScoreKernelArgs k;           // sv: the long sequences of one bucket (no mask: a sequence outside it has no tiles)
+    const uint32_t* tile_off;    // [sv.count + 1] prefix sums of the sequences' tile counts
+    uint32_t n_tiles, stride;    // tile_off[sv.count]; windows a tile emits (score_tile_geometry)
+    float*   tile_best;          // [n_tiles] a tile's maximum ...
+    uint32_t* tile_idx;          // ... and the first window of the sequence that reaches it
+};
+// the one tile geometry for motifs of width W; false when W leaves no stride of at least 16
+bool score_tile_geometry(uint32_t W, uint32_t* tile_positions, uint32_t* stride);
+uint32_t score_tile_threads();
+// k_score_tile over every tile, then the per-sequence maxima into k.zoops / k.z
+int launch_score_tiles(const ScoreTileArgs& a, uint32_t blocks, hipStream_t st);
+
 
 // ---- window p-values on the device (occ.hip; ScoreSeqSet.cpp:70-126) ----
 struct OccCand {                 // a positive window the host has to look at

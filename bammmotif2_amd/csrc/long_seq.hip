@@ -3,11 +3,14 @@
 //
 //   k_long_em     EM::EStep   refinement/EM.cpp:149-196, EM::MStep EM.cpp:231-243, the sum over r of
 //                 EM::optimize_q EM.cpp:509-513, EM::getR's layout EM.cpp:173
-//   k_long_score  ScoreSeqSet::calcLogOdds  seq_scoring/ScoreSeqSet.cpp:41-66
+//   k_long_score  ScoreSeqSet::calcLogOdds  seq_scoring/ScoreSeqSet.cpp:41-66 -- the scorer of the log-odds tables
+//                 beyond the LDS (any length then) and of long records under bamm_ctx_set_tuning("score_tiles", 0);
+//                 while the table fits the LDS, long records are scored tile by tile on the whole GPU instead
+//                 (score_tile.hip; score.cpp: score_route)
 //
 // The reference has no length limit (init/Sequence.cpp:4-43); the fast kernels hold a sequence in the
 // registers of one wavefront.  Records this long are rare in motif discovery (ChIP-seq peaks are a few
-// hundred bp), so this path is written for coverage, not speed: every window multiplies its W odds straight
+// hundred bp; a scanner's contigs and chromosomes take the tiles), so this path is written for coverage, not speed: every window multiplies its W odds straight
 // from the table in global memory (L2-resident, any order K), k-mers are read from the 2-bit stream with a
 // binary search of the sequence's N-exception list, two passes (partition sum, then responsibilities), and
 // the fixed-point addends go directly into the pass's global accumulator -- the same integers the fast

@@ -1,6 +1,7 @@
 // The scorer of the C ABI: the seed model's counts from a PWM (Motif::initFromPWM) and the log-odds scores of a model
 // over a resident set (ScoreSeqSet::calcLogOdds).  Host code only.
 
+#include <climits>
 #include <cmath>
 
 #include "handles.h"
@@ -8,6 +9,35 @@
 using namespace bamm;
 
 namespace bamm {
+
+namespace {
+
+// The scorer a length bucket takes: k_score while a sequence fits one wavefront's registers, beyond that the same chain
+// tile by tile (score_tile.hip) -- both with the log-odds table in LDS --, and the window-by-window scorer (long_seq.hip),
+// which reads the table from global memory, for tables beyond the LDS of a CU (orders >= 6 at usual widths), for widths
+// that leave a tile no stride, and for long sequences under bamm_ctx_set_tuning("score_tiles", 0).
+enum class ScoreRoute { kWave, kTiles, kWindows };
+ScoreRoute score_route(const bamm_ctx* c, const Bucket& bk, uint32_t K, uint32_t W) {
+    if ((size_t)W * (ipow4(K + 1) + 1) * sizeof(float) > 160u * 1024u) return ScoreRoute::kWindows;
+    if (bk.mclass != kLongClass) return ScoreRoute::kWave;
+    return c->use_score_tiles && score_tile_geometry(W, nullptr, nullptr) ? ScoreRoute::kTiles : ScoreRoute::kWindows;
+}
+
+// prefix sums of the tile counts of a long bucket's sequences, ceil((L - W + 1) / stride) each and none for a sequence the
+// mask leaves out: one entry per long sequence, nothing proportional to their length.  Returns the number of tiles.
+uint64_t bucket_tiles(const bamm_seqs* s, const Bucket& bk, const uint8_t* seq_mask, uint32_t W, uint32_t stride,
+                      std::vector<uint32_t>* off) {
+    uint64_t tiles = 0;
+    if (off) off->assign((size_t)bk.count + 1, 0u);
+    for (uint32_t t = 0; t < bk.count; t++) {
+        const uint64_t seq = bk.h_idx.empty() ? t : bk.h_idx[t];
+        if (!seq_mask || seq_mask[seq]) tiles += ((uint64_t)s->h_len[seq] - W + stride) / stride;
+        if (off) (*off)[t + 1] = (uint32_t)std::min<uint64_t>(tiles, UINT32_MAX);
+    }
+    return tiles;
+}
+
+}  // namespace
 
 int score_on_device(bamm_ctx* c, bamm_seqs* s, const uint8_t* seq_mask, uint32_t K, uint32_t W, uint32_t bg_order, const float* v,
                     const float* vbg, bool want_mops, bool pooled_mops, DevBlocks& tmp, DeviceScores* out) {
@@ -46,9 +76,26 @@ int score_on_device(bamm_ctx* c, bamm_seqs* s, const uint8_t* seq_mask, uint32_t
         ScoreKernelArgs a{};
         a.sv = make_view(s, exc, bk.d_idx, bk.count, d_smask);
         a.K = K; a.W = W; a.Y = Y; a.s = d_tab; a.mops = d_mops; a.mops_off = d_moff; a.zoops = d_zoops; a.z = d_z;
-        // beyond the length classes, or a log-odds table beyond the LDS of a CU (orders >= 6 at usual widths): the
-        // window-by-window scorer reads the table from global memory, same sums in the same order
-        if (bk.mclass == kLongClass || (size_t)W * Ys * sizeof(float) > 160u * 1024u) {
+        ScoreRoute route = score_route(c, bk, K, W);
+        if (route == ScoreRoute::kTiles) {
+            ScoreTileArgs ta{};
+            std::vector<uint32_t> toff;
+            (void)score_tile_geometry(W, nullptr, &ta.stride);
+            const uint64_t tiles = bucket_tiles(s, bk, seq_mask, W, ta.stride, &toff);
+            if (tiles == 0) continue;                        // every long sequence is outside the mask
+            if (tiles <= UINT32_MAX) {
+                uint32_t* d_toff = nullptr;
+                ta.n_tiles = (uint32_t)tiles;
+                if ((rc = tmp.upload(&d_toff, toff.data(), toff.size())) || (rc = tmp.alloc(&ta.tile_best, tiles)) ||
+                    (rc = tmp.alloc(&ta.tile_idx, tiles))) return rc;
+                ta.k = a; ta.k.sv.mask = nullptr; ta.tile_off = d_toff;
+                const uint32_t waves = score_tile_threads() / 64u;
+                rc = launch_score_tiles(ta, std::min(default_blocks(c, score_tile_threads()), (ta.n_tiles + waves - 1) / waves), st);
+                continue;
+            }
+            route = ScoreRoute::kWindows;                    // (more tiles than a launch indexes: 2^32 of them)
+        }
+        if (route == ScoreRoute::kWindows) {                 // same sums in the same order, the table read from global memory
             rc = launch_long_score(a, std::min(bk.count, (uint32_t)std::max(1, c->num_cus) * 8u), st);
             continue;
         }
@@ -64,6 +111,38 @@ int score_on_device(bamm_ctx* c, bamm_seqs* s, const uint8_t* seq_mask, uint32_t
 }  // namespace bamm
 
 extern "C" {
+
+int bamm_score_tile_geometry(uint32_t W, uint32_t* tile_positions, uint32_t* stride) {
+    if (!score_tile_geometry(W, tile_positions, stride)) {
+        set_error("bamm_score_tile_geometry: W=%u leaves a tile no stride of at least 16 positions", W);
+        return BAMM_ERR_ARG;
+    }
+    return BAMM_OK;
+}
+
+int bamm_score_plan(bamm_ctx* c, const bamm_seqs* s, uint32_t K, uint32_t W, uint64_t* wave_seqs, uint64_t* tiled_seqs,
+                    uint64_t* tiles, uint64_t* window_seqs) {
+    if (!c || !s) { set_error("bamm_score_plan: null argument"); return BAMM_ERR_ARG; }
+    if (K > BAMM_MAX_ORDER || W == 0) { set_error("bamm_score_plan: bad K/W"); return BAMM_ERR_ARG; }
+    if (s->ctx != c) { set_error("sequence set belongs to another context"); return BAMM_ERR_ARG; }
+    if (s->n && s->min_len < W) { set_error("a sequence is shorter than the motif (W=%u)", W); return BAMM_ERR_ARG; }
+    uint64_t n[3] = {0, 0, 0}, nt = 0;
+    uint32_t stride = 0;
+    for (const Bucket& bk : s->buckets) {
+        ScoreRoute route = score_route(c, bk, K, W);
+        if (route == ScoreRoute::kTiles) {
+            (void)score_tile_geometry(W, nullptr, &stride);
+            const uint64_t t = bucket_tiles(s, bk, nullptr, W, stride, nullptr);
+            if (t <= UINT32_MAX) nt += t; else route = ScoreRoute::kWindows;
+        }
+        n[(int)route] += bk.count;
+    }
+    if (wave_seqs) *wave_seqs = n[(int)ScoreRoute::kWave];
+    if (tiled_seqs) *tiled_seqs = n[(int)ScoreRoute::kTiles];
+    if (tiles) *tiles = nt;
+    if (window_seqs) *window_seqs = n[(int)ScoreRoute::kWindows];
+    return BAMM_OK;
+}
 
 int bamm_seed_from_pwm(bamm_ctx* c, bamm_seqs* s, uint32_t K, uint32_t W, const float* score, float q, const double* u,
                        int32_t* counts, uint32_t* z) {

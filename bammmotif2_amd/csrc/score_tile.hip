@@ -1,0 +1,220 @@
+// Long sequences through the register-resident scorer, tile by tile.
+//
+//   k_score_tile         ScoreSeqSet::calcLogOdds seq_scoring/ScoreSeqSet.cpp:41-66 over one tile of one long sequence
+//   k_score_tile_reduce  the sequence's maximum (ScoreSeqSet.cpp:46-57) over its tiles
+//
+// A window's score is W additions, left to right, of table entries picked by the k-mers inside the window: it depends on
+// nothing else in the sequence.  So a sequence beyond the length classes (more than 8192 positions) is cut into tiles of
+// 64 * M positions that overlap by at least W - 1, and a wavefront runs on one tile the chain k_score (kernels.hip) runs
+// on one short sequence: the same LDS table [W][Y+1], the same U[m] = U[m-1] + sj[y[m]] with wave_shr1 across lanes --
+// the same sums in the same order, bit for bit what k_long_score (long_seq.hip) and the reference give.  A tile starts on a
+// multiple of the stride, the stride is a multiple of 16 (a tile starts on a word of the 2-bit stream) and at most
+// 64 * M - (W - 1); a tile emits the windows that start in [t0, t0 + stride), the sequence's last tile up to L - W.
+//
+// A tile is found from its index: the launch carries the prefix sums of the bucket's tile counts, one entry per long
+// sequence, and a wave searches them.  A sequence the mask leaves out has no tiles.
+//
+// The maximum: every tile leaves (best, first window that reaches it), the reduction folds a sequence's tiles with the
+// scorer's rule (strict >, the lowest index among equals) -- no float atomics, nothing that depends on scheduling.
+//
+// This unit is compiled with the flags of kernels.hip's scorer (no contraction, no fast math): the additions are IEEE fp32.
+#include "device_utils.h"
+
+#include <algorithm>
+#include <cfloat>
+
+// The one geometry (positions per lane, threads per block: a class of BAMM_FOR_EACH_MCLASS in kernels.hip), chosen by
+// measurement (profiles/score_tiles_ab.txt).  tools/score_tiles_ab.py builds the other candidates by overriding the two.
+#ifndef BAMM_SCORE_TILE_M
+#define BAMM_SCORE_TILE_M 32
+#define BAMM_SCORE_TILE_THREADS 512
+#endif
+
+namespace bamm {
+namespace {
+
+constexpr int kTileM = BAMM_SCORE_TILE_M, kTileThreads = BAMM_SCORE_TILE_THREADS;
+constexpr uint32_t kTilePositions = 64u * (uint32_t)kTileM;
+static_assert(kTileThreads % 64 == 0 && kTileThreads <= 1024, "whole waves");
+
+// decode_positions' arithmetic (device_utils.h) for the positions t0 + lane*M + m of a sequence, t0 a multiple of 16:
+// y[m] = kmer_[t0 + lane*M + m] mod Y (Sequence.cpp:35-41).  The word in front of the tile is read when t0 > 0 (a
+// position's k-mer reaches up to K <= 10 bases back); it is zero at the start of a sequence.  Of the sequence's
+// exceptions only those inside the tile are visited: one binary search for the first, then the run up to the tile's end
+// -- never the whole list, which holds millions of entries for a chromosome.  (Kept apart from decode_positions so that
+// the kernels built on that one compile to what they did.)
+template <int M>
+__device__ __forceinline__ void decode_tile(const SeqView& sv, uint32_t seq, uint32_t L, uint32_t Y, uint32_t t0, int lane,
+                                            uint32_t (&y)[M]) {
+    constexpr int NSEL = (M + 14) / 16 + 1;  // candidate words per position
+    const uint32_t* wp = sv.words + sv.word_off[seq] + (t0 >> 4);
+    const uint32_t nw = ((L + 15u) >> 4) - (t0 >> 4);        // words from the tile's first to the sequence's last
+    const uint32_t p0 = (uint32_t)lane * M;
+    const uint32_t wi0 = p0 >> 4;
+    uint32_t w[NSEL + 1];  // w[0] = word wi0-1, w[1] = word wi0, ...
+    if (wi0 >= 1u) w[0] = (wi0 - 1u < nw) ? wp[wi0 - 1u] : 0u;
+    else w[0] = t0 ? *(wp - 1) : 0u;
+#pragma unroll
+    for (int i = 0; i < NSEL; i++) w[i + 1] = (wi0 + i < nw) ? wp[wi0 + i] : 0u;
+#pragma unroll
+    for (int m = 0; m < M; m++) {
+        const uint32_t p = p0 + m;                           // (t0 + p) & 15 == p & 15
+        const uint32_t sel = (p >> 4) - wi0;
+        uint32_t lo = w[1], hi = w[0];
+#pragma unroll
+        for (int c = 1; c < NSEL; c++) {
+            lo = (sel == (uint32_t)c) ? w[c + 1] : lo;
+            hi = (sel == (uint32_t)c) ? w[c] : hi;
+        }
+        const uint32_t sh = 30u - 2u * (p & 15u);
+        y[m] = __builtin_amdgcn_alignbit(hi, lo, sh) & (Y - 1u);
+    }
+    // positions whose k-mer the 2-bit stream cannot express (N randomisation, Sequence.cpp:38), rebased by t0
+    const uint64_t e1 = sv.exc_off[seq + 1];
+    uint64_t e = sv.exc_off[seq], hi = e1;
+    while (e < hi) {                                         // first exception at or behind t0
+        const uint64_t mid = e + ((hi - e) >> 1);
+        if (sv.exc[mid].x < t0) e = mid + 1u; else hi = mid;
+    }
+    for (; e < e1; e++) {                                    // a tile inside a run of N: 64 * M of them (slow, accepted)
+        const uint2 x = sv.exc[e];
+        const uint32_t pos = __builtin_amdgcn_readfirstlane(x.x) - t0, val = __builtin_amdgcn_readfirstlane(x.y);
+        if (pos >= 64u * (uint32_t)M) break;
+        if constexpr (M >= 10 && M <= 32) {                  // one indexed register write in the owning lane (see decode_raw)
+            const uint32_t owner = pos / (uint32_t)M, slot = pos % (uint32_t)M;
+            if ((uint32_t)lane == owner) y[slot] = val;
+        } else {
+            const uint32_t mm = pos - p0;
+#pragma unroll
+            for (int m = 0; m < M; m++) y[m] = (mm == (uint32_t)m) ? val : y[m];
+        }
+    }
+}
+
+// the bucket slot whose tiles include tile g: the last t with tile_off[t] <= g (sequences without tiles are stepped over)
+__device__ __forceinline__ uint32_t tile_owner(const uint32_t* tile_off, uint32_t count, uint32_t g) {
+    uint32_t lo = 0, hi = count;                             // tile_off[lo] <= g < tile_off[hi]
+    while (hi - lo > 1u) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (tile_off[mid] <= g) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
+template <int M, int THREADS>
+__global__ void __launch_bounds__(THREADS) k_score_tile(ScoreTileArgs a) {
+    extern __shared__ float lds[];
+    const uint32_t W = a.k.W, Y = a.k.Y, Ys = a.k.Y + 1u;
+    float* s_lds = lds;                                  // [W][Y+1], row Y = 0.0f
+    for (uint32_t i = threadIdx.x; i < W * Ys; i += blockDim.x) s_lds[i] = a.k.s[i];
+    __syncthreads();
+
+    const int lane = threadIdx.x & 63;
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint32_t waves_per_block = blockDim.x >> 6;
+    const uint32_t total_waves = gridDim.x * waves_per_block;
+
+    for (uint32_t g = blockIdx.x * waves_per_block + wave; g < a.n_tiles; g += total_waves) {
+        const uint32_t t = tile_owner(a.tile_off, a.k.sv.count, g);
+        const uint32_t seq = pick_sequence(a.k.sv, t);
+        const uint32_t L = a.k.sv.len[seq];
+        const uint32_t t0 = (g - a.tile_off[t]) * a.stride;
+        const uint32_t n_emit = min(a.stride, L - W + 1u - t0);   // windows t0 .. t0 + n_emit - 1 are this tile's
+        const uint32_t p0 = (uint32_t)lane * M;
+        uint32_t y[M];
+        decode_tile<M>(a.k.sv, seq, L, Y, t0, lane, y);
+
+        float U[M];                                          // k_score's chain (kernels.hip), on the tile
+        const float* sj = s_lds;
+#pragma unroll
+        for (int m = 0; m < M; m++) U[m] = sj[y[m]];        // 0.0f + s == s
+        for (uint32_t j = 1; j < W; j++) {
+            sj += Ys;
+            const float carry = wave_shr1(0.0f, U[M - 1]);
+#pragma unroll
+            for (int m = M - 1; m >= 1; m--) U[m] = U[m - 1] + sj[y[m]];
+            U[0] = carry + sj[y[0]];
+        }
+        float best = -FLT_MAX;                              // ScoreSeqSet.cpp:46
+        uint32_t best_i = 0;
+        float* mo = a.k.mops ? a.k.mops + a.k.mops_off[seq] + t0 : nullptr;
+#pragma unroll
+        for (int m = 0; m < M; m++) {
+            const uint32_t p = p0 + m;                       // U[m]: the window that ends at tile position p
+            if (p + 1u >= W && p + 1u - W < n_emit) {
+                const uint32_t i = p + 1u - W;
+                if (mo) mo[i] = U[m];
+                if (U[m] > best) { best = U[m]; best_i = t0 + i; }
+            }
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {                  // first arg-max over the wave
+            const float ob = __shfl_xor(best, o, 64);
+            const uint32_t oi = __shfl_xor(best_i, o, 64);
+            const bool take = (ob > best) || (ob == best && oi < best_i);
+            best = take ? ob : best;
+            best_i = take ? oi : best_i;
+        }
+        if (lane == 0) { a.tile_best[g] = best; a.tile_idx[g] = best_i; }
+    }
+}
+
+// a wave per sequence: lane l folds tiles l, l + 64, ... in ascending order (strict >: the first maximum stays), then the
+// lanes' results fold with the lowest index among equals -- what one walk over the tiles in ascending order leaves
+__global__ void __launch_bounds__(256) k_score_tile_reduce(ScoreTileArgs a) {
+    const int lane = threadIdx.x & 63;
+    const uint32_t waves_per_block = blockDim.x >> 6, total_waves = gridDim.x * waves_per_block;
+    for (uint32_t t = blockIdx.x * waves_per_block + (threadIdx.x >> 6); t < a.k.sv.count; t += total_waves) {
+        const uint32_t g0 = a.tile_off[t], g1 = a.tile_off[t + 1u];
+        if (g0 == g1) continue;                             // outside the mask: the zeros stay
+        float best = -FLT_MAX;
+        uint32_t best_i = 0;
+        for (uint32_t g = g0 + (uint32_t)lane; g < g1; g += 64u) {
+            const float b = a.tile_best[g];
+            if (b > best) { best = b; best_i = a.tile_idx[g]; }
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const float ob = __shfl_xor(best, o, 64);
+            const uint32_t oi = __shfl_xor(best_i, o, 64);
+            const bool take = (ob > best) || (ob == best && oi < best_i);
+            best = take ? ob : best;
+            best_i = take ? oi : best_i;
+        }
+        if (lane == 0) {
+            const uint32_t seq = pick_sequence(a.k.sv, t);
+            a.k.zoops[seq] = best;
+            a.k.z[seq] = best_i;
+        }
+    }
+}
+
+}  // namespace
+
+bool score_tile_geometry(uint32_t W, uint32_t* tile_positions, uint32_t* stride) {
+    if (W == 0 || W > kTilePositions) return false;
+    const uint32_t st = (kTilePositions - (W - 1u)) & ~15u;  // the largest multiple of 16 that leaves an overlap of W - 1
+    if (st < 16u) return false;
+    if (tile_positions) *tile_positions = kTilePositions;
+    if (stride) *stride = st;
+    return true;
+}
+
+uint32_t score_tile_threads() { return (uint32_t)kTileThreads; }
+
+int launch_score_tiles(const ScoreTileArgs& a, uint32_t blocks, hipStream_t st) {
+    if (a.n_tiles == 0) return BAMM_OK;
+    const size_t lds = (size_t)a.k.W * (a.k.Y + 1) * sizeof(float);
+    uint32_t tp = 0, stride = 0;
+    if (lds > 160 * 1024 || !score_tile_geometry(a.k.W, &tp, &stride) || stride != a.stride || blocks == 0) {
+        set_error("k_score_tile: W=%u, stride %u, a table of %zu bytes or %u blocks is outside the tiles' envelope", a.k.W, a.stride, lds, blocks);
+        return BAMM_ERR_ARG;
+    }
+    if (int rc = launch_kernel(&k_score_tile<kTileM, kTileThreads>, blocks, (uint32_t)kTileThreads, lds, st, a)) return rc;
+    BAMM_HIP(hipGetLastError());
+    hipLaunchKernelGGL(k_score_tile_reduce, dim3(std::min((a.k.sv.count + 3u) / 4u, 1024u)), dim3(256), 0, st, a);
+    BAMM_HIP(hipGetLastError());
+    return BAMM_OK;
+}
+
+}  // namespace bamm

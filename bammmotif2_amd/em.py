@@ -613,6 +613,22 @@ def logodds(ctx: Context, seqs: SeqSet, K: int, W: int, bg_order: int, v, vbg, w
     return (mops[:total] if want_mops else None), zoops[:N], z[:N]
 
 
+def score_tile_geometry(W: int):
+    """(tile_positions, stride) of the tiles the scorer cuts a sequence beyond 8192 positions into for motifs of width W
+    (bamm_score_tile_geometry: a pure function, no device needed); BammError for a W that leaves no stride."""
+    tp, stride = C.c_uint32(), C.c_uint32()
+    check(abi.load().bamm_score_tile_geometry(W, C.byref(tp), C.byref(stride)))
+    return tp.value, stride.value
+
+
+def score_plan(ctx: Context, seqs: SeqSet, K: int, W: int) -> dict:
+    """Which scorer the sequences of `seqs` take under the context's tuning (bamm_score_plan): `wave_seqs` in one wavefront's
+    registers, `tiled_seqs` cut into `tiles` tiles, `window_seqs` window by window."""
+    out = [C.c_uint64() for _ in range(4)]
+    check(ctx.lib.bamm_score_plan(ctx.h, seqs.h, K, W, *(C.byref(x) for x in out)))
+    return dict(zip(("wave_seqs", "tiled_seqs", "tiles", "window_seqs"), (x.value for x in out)))
+
+
 class Occurrences:
     """What bamm_occurrences returns: per hit `seq`, `pos` (window start, 0-based), `score`, `fp`, `p`, `e`, and the scalars
     of ScoreSeqSet::calcPvalues (`n_neg_scores`, `n_top`, `s_ntop`, `lambda_`) with the number of windows the device handed

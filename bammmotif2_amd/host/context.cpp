@@ -49,6 +49,10 @@ bamm_ctx* WarmUp::take(int device_) {
 void Run::make_ctx(Dev& dv) {
     if (!dv.ctx) dv.ctx = warm.take(dv.device);             // the one the warm-up made
     if (!dv.ctx && bamm_ctx_create(dv.device, nullptr, &dv.ctx)) die_abi("no usable MI355X");
+    // BAMM_NO_SCORE_TILES=1: long records window by window, as before the tiles -- for comparing this program with itself
+    // (the library reads no environment: the driver turns the variable into the tuning key)
+    if (const char* e = std::getenv("BAMM_NO_SCORE_TILES"); e && *e && *e != '0')
+        if (bamm_ctx_set_tuning(dv.ctx, "score_tiles", 0)) die_abi("score_tiles");
 }
 
 namespace {

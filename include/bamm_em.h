@@ -141,6 +141,9 @@ int  bamm_ctx_set_launch(bamm_ctx* ctx, uint32_t blocks, uint32_t threads_per_bl
  *                       pass p+1's first kernel instead of a launch of its own (default 1; K <= 2-sized tables)
  *   "update_blocks" 1/0 tables beyond the update's LDS form (k >= 3 at usual widths): the model update spread over
  *                       blocks in three short launches instead of one block (default 1; same model bits)
+ *   "score_tiles"  1/0  the scorer (bamm_logodds*, bamm_occurrences, bamm_fdr_add_set) takes sequences longer than
+ *                       BAMM_MAX_SEQ_POSITIONS tile by tile through the register-resident kernel (default 1; 0 = window by
+ *                       window, one workgroup per sequence; the same bits); read at the scoring call
  *   "scratch_cache_mb" n  idle set-sized scratch blocks (dense r, lists, logs) a context keeps for its next handle
  *                       instead of freeing them (default: a quarter of the device's memory; 0 = keep nothing)
  *   "scratch_poison" 1/0 tests: fill every such block with 0xFF bytes when it is handed out (default 0)
@@ -156,8 +159,11 @@ long long bamm_device_blocks_live(void);
 /* ------------------------------------------------------------------ sequences ----------- */
 /* Uploads sequences [begin,end) of `p`; they stay resident and are shared (ref-counted) by
  * any number of EM handles -- CV folds pass a mask instead of copying (FDR.cpp:49-57).
- * Any length: sequences up to BAMM_MAX_SEQ_POSITIONS go through the register-resident kernels, longer
- * ones through a window-by-window path with identical results (EM passes, getR, the scorer);
+ * Any length: sequences up to BAMM_MAX_SEQ_POSITIONS go through the register-resident kernels.  Longer ones: EM passes
+ * and getR walk them window by window, one workgroup per sequence; the scorer cuts them into overlapping tiles of
+ * bamm_score_tile_geometry's size, one wavefront per tile on the whole GPU, while the log-odds table fits the LDS
+ * (W * (4^(K+1) + 1) * 4 <= 160 KiB: up to order 5 at usual widths), and walks them window by window beyond that
+ * (bamm_score_plan reports the split) -- identical results on every path;
  * bamm_seed_from_pwm and bamm_em_mask keep per-wave arrays over one sequence: in LDS up to about
  * 10 000 / 16 000 positions, in a global scratch region per wave beyond (same arithmetic, slower;
  * bamm_em_mask's window lists are 32 bits wide there, and from order 7 on its counts go straight into
@@ -411,6 +417,18 @@ int  bamm_logodds(bamm_ctx* ctx, bamm_seqs* seqs, uint32_t K, uint32_t W, uint32
 int  bamm_logodds_subset(bamm_ctx* ctx, bamm_seqs* seqs, const uint8_t* seq_mask, uint32_t K, uint32_t W,
                          uint32_t bg_order, const float* v_flat, const float* vbg, float* mops,
                          uint64_t mops_cap, float* zoops, uint64_t* z);
+
+/* The tiles the scorer cuts a sequence longer than BAMM_MAX_SEQ_POSITIONS into, for motifs of width W: a tile holds
+ * tile_positions consecutive positions and starts on a multiple of stride (a multiple of 16, at most
+ * tile_positions - (W - 1)); it scores the windows that start in its first `stride` positions, the sequence's last tile
+ * up to window L - W.  Pure host arithmetic, no device needed; either pointer may be NULL.  BAMM_ERR_ARG for W = 0 and
+ * for a W that leaves no stride of at least 16 (such motifs are scored window by window).                          */
+int  bamm_score_tile_geometry(uint32_t W, uint32_t* tile_positions, uint32_t* stride);
+/* Which kernel the scorer takes for the sequences of `seqs` with a model of order K and width W, under the context's
+ * tuning as it stands: sequences held in one wavefront's registers, sequences cut into tiles (and the number of tiles,
+ * without a sequence mask), sequences walked window by window with the table in global memory.  Any pointer may be NULL. */
+int  bamm_score_plan(bamm_ctx* ctx, const bamm_seqs* seqs, uint32_t K, uint32_t W, uint64_t* wave_seqs,
+                     uint64_t* tiled_seqs, uint64_t* tiles, uint64_t* window_seqs);
 
 /* ------------------------------------------------------------------ occurrences --------- */
 /* ScoreSeqSet::calcPvalues + the cut of ScoreSeqSet::write (ScoreSeqSet.cpp:70-126, :245-291): every window of the
