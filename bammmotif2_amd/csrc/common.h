@@ -296,7 +296,7 @@ struct ScoreKernelArgs {
     uint32_t* z;                 // [N]
 };
 
-// ---- long sequences through the register-resident scorer, tile by tile (score_tile.hip) ----
+// ---- long sequences through the register-resident scorer, tile by tile (scorer.hip) ----
 struct ScoreTileArgs {
     ScoreKernelArgs k;           // sv: the long sequences of one bucket (no mask: a sequence outside it has no tiles)
     const uint32_t* tile_off;    // [sv.count + 1] prefix sums of the sequences' tile counts
@@ -464,6 +464,7 @@ size_t m_list_lds_bytes(uint32_t cols, uint32_t Y, uint32_t logC, int M, uint32_
 // sequences beyond the length classes (long_seq.hip): one workgroup per sequence, window by window
 int launch_long_em(const EmKernelArgs& a, bool accum, bool write_r, bool slot_layout, uint32_t blocks, hipStream_t st);
 int launch_long_score(const ScoreKernelArgs& a, uint32_t blocks, hipStream_t st);
+// the scorer of the length classes (scorer.hip)
 int launch_score(int mclass, const ScoreKernelArgs& a, uint32_t blocks, uint32_t threads,
                  hipStream_t st);
 // EM::mask only: its kernels still leave one partial table per block; summed into the fused accumulator

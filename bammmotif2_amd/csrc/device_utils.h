@@ -1,6 +1,7 @@
-// Device-side helpers shared by the sequence kernels (kernels.hip, grouped.hip): DPP wave shifts,
-// the 2^-40 fixed-point conversion, hand-issued LDS gathers / predicated LDS adds and the 2-bit
-// sequence decode.  Everything is `__device__ __forceinline__` in an anonymous namespace.
+// Device-side helpers shared by the sequence kernels (kernels.hip, grouped.hip, scorer.hip): DPP wave shifts,
+// the 2^-40 fixed-point conversion, hand-issued LDS gathers / predicated LDS adds, the 2-bit
+// sequence decode and the cold paths' (seed.hip, mask.hip, long_seq.hip) position-by-position decode.
+// Everything is `__device__ __forceinline__` in an anonymous namespace.
 #pragma once
 #include "common.h"
 
@@ -189,6 +190,28 @@ __device__ __forceinline__ float wave_sum(float x) {
     const float r3 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(xi, 48));
     return (r0 + r1) + (r2 + r3);
 }
+// The first arg-max over the wave, in every lane: the larger value wins (strict >), among equals the lowest index --
+// the scorer's rule, ScoreSeqSet.cpp:46-59, which decides z.  (By value: with `best` passed by reference the emit loop in
+// front of the call kept up to 60 more VGPRs in k_score.)
+struct WaveMax { float best; uint32_t best_i; };
+__device__ __forceinline__ WaveMax wave_first_max(float best, uint32_t best_i) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float ob = __shfl_xor(best, o, 64);
+        const uint32_t oi = __shfl_xor(best_i, o, 64);
+        const bool take = (ob > best) || (ob == best && oi < best_i);
+        best = take ? ob : best;
+        best_i = take ? oi : best_i;
+    }
+    return {best, best_i};
+}
+// LDS written by some lanes of a wave, read by others (the grouped and mixed-row kernels, seed.hip, mask.hip): DS operations of one wave retire in order; this only stops the
+// compiler from moving LDS reads above the writes of other lanes
+__device__ __forceinline__ void wave_lds_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
 
 // ---- sequence decode: M consecutive positions of one sequence into registers -------------
 // y[m] = kmer_[p] mod Y for p = lane*M+m (Sequence.cpp:35-41), PAD (= Y) where p >= limit.
@@ -321,6 +344,27 @@ __device__ __forceinline__ void decode_raw(const RawSeq<M>& r, const SeqView& sv
     }
 #pragma unroll
     for (int m = 0; m < M; m++) y[m] = (p0 + m < limit) ? y[m] : Y;
+}
+
+// ---- the cold paths' decode: one position at a time (seed.hip, mask.hip, long_seq.hip) -----
+// kmer_[p] mod Y (Sequence.cpp:35-41) from the 2-bit stream wp of one sequence, N exceptions not applied
+__device__ __forceinline__ uint32_t stream_kmer(const uint32_t* wp, uint32_t p, uint32_t Y) {
+    const uint32_t wi = p >> 4;
+    const uint32_t lo = wp[wi], hi = wi ? wp[wi - 1u] : 0u;
+    return __builtin_amdgcn_alignbit(hi, lo, 30u - 2u * (p & 15u)) & (Y - 1u);
+}
+// kmer_[p] mod Y for every position of one sequence into the wave's ybuf[L], N exceptions applied
+__device__ __forceinline__ void decode_to_lds(const SeqView& sv, uint32_t seq, uint32_t L, uint32_t Y, int lane,
+                                              uint32_t* ybuf) {
+    const uint32_t* wp = sv.words + sv.word_off[seq];
+    for (uint32_t p = (uint32_t)lane; p < L; p += 64u) ybuf[p] = stream_kmer(wp, p, Y);
+    wave_lds_sync();
+    const uint64_t e0 = sv.exc_off[seq], e1 = sv.exc_off[seq + 1];
+    for (uint64_t e = e0 + (uint64_t)lane; e < e1; e += 64u) {       // N randomisation (Sequence.cpp:38)
+        const uint2 x = sv.exc[e];
+        if (x.x < L) ybuf[x.x] = x.y;
+    }
+    wave_lds_sync();
 }
 
 }  // namespace

@@ -58,13 +58,6 @@
 namespace bamm {
 namespace {
 
-__device__ __forceinline__ void wave_lds_sync() {
-    // DS operations of one wave retire in order; this only pins the compiler's ordering
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 // Entry of the fix lanes' log (kernels with no LDS for the bins of their virtual rows): 8 bytes
 //   low word  = the sum as a float.  It is what ONE window added to a virtual count cell: to_fixed40_pre() of an
 //               fp32 responsibility, i.e. an integer of at most 24 significant bits -- the conversion to float and

@@ -102,7 +102,7 @@ struct bamm_ctx {
     uint32_t blocks = 0, threads = 0;   // 0 = default
     // bamm_ctx_set_tuning: kernel-selection switches for benchmarks and the cross-kernel parity tests
     bool use_grouped = true, use_sparse = true, use_e_fused = true, use_e_list = true, use_fused_update = true, use_adaptive_lists = true, use_update_blocks = true;
-    bool use_score_tiles = true;        // the scorer takes sequences beyond the length classes tile by tile (score_tile.hip); read at every scoring call
+    bool use_score_tiles = true;        // the scorer takes sequences beyond the length classes tile by tile (scorer.hip); read at every scoring call
     uint32_t list_threshold_pct = 45;   // sliced path: a pass takes lists when fewer than this share of the windows was non-zero in the pass before
     uint32_t group_size = 0;            // 0 = planner's choice
     int group_layout = -1;              // -1 = planner's choice

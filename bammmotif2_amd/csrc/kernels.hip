@@ -5,7 +5,7 @@
 //                   EM::MStep  refinement/EM.cpp:231-243   (order-K fractional counts)
 //                   EM::optimize_q's sum over r            refinement/EM.cpp:509-513
 //   (the model update, the odds table and the reductions: model.hip)
-//   k_score         ScoreSeqSet::calcLogOdds seq_scoring/ScoreSeqSet.cpp:41-66
+//   (the log-odds scorer, k_score: scorer.hip)
 //
 //   k_e_slice / k_m_slice  the same two chains cut into column ranges for tables beyond one
 //                   CU's LDS (k >= 4), chain state and r in HBM
@@ -23,10 +23,9 @@
 // table is written.  No MFMA: this is gather/scatter, not a contraction.
 
 #include "device_utils.h"
+#include "mclass.h"
 
 #include <algorithm>
-#include <cfloat>
-#include <type_traits>
 
 namespace bamm {
 
@@ -706,64 +705,6 @@ __global__ void __launch_bounds__(THREADS) k_m_list(EmKernelArgs a, uint32_t j0,
     }
 }
 
-// ---- log-odds scorer ----------------------------------------------------------------------
-template <int M, int THREADS>
-__global__ void __launch_bounds__(THREADS) k_score(ScoreKernelArgs a) {
-    extern __shared__ float lds[];
-    const uint32_t W = a.W, Y = a.Y, Ys = a.Y + 1u;
-    float* s_lds = lds;                                  // [W][Y+1], row Y = 0.0f
-    for (uint32_t i = threadIdx.x; i < W * Ys; i += blockDim.x) s_lds[i] = a.s[i];
-    __syncthreads();
-
-    const int lane = threadIdx.x & 63;
-    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const uint32_t waves_per_block = blockDim.x >> 6;
-    const uint32_t total_waves = gridDim.x * waves_per_block;
-
-    for (uint32_t t = blockIdx.x * waves_per_block + wave; t < a.sv.count; t += total_waves) {
-        const uint32_t seq = pick_sequence(a.sv, t);
-        if (a.sv.mask && !a.sv.mask[seq]) continue;
-        const uint32_t L = a.sv.len[seq];
-        const uint32_t p0 = (uint32_t)lane * M;
-        uint32_t y[M];
-        decode_positions<M>(a.sv, seq, L, Y, L, lane, y);   // full windows (ScoreSeqSet.cpp:49-54)
-
-        float U[M];
-        const float* sj = s_lds;
-#pragma unroll
-        for (int m = 0; m < M; m++) U[m] = sj[y[m]];        // 0.0f + s == s
-        for (uint32_t j = 1; j < W; j++) {
-            sj += Ys;
-            const float carry = wave_shr1(0.0f, U[M - 1]);
-#pragma unroll
-            for (int m = M - 1; m >= 1; m--) U[m] = U[m - 1] + sj[y[m]];
-            U[0] = carry + sj[y[0]];
-        }
-        float best = -FLT_MAX;                              // ScoreSeqSet.cpp:46
-        uint32_t best_i = 0;
-        float* mo = a.mops ? a.mops + a.mops_off[seq] : nullptr;
-#pragma unroll
-        for (int m = 0; m < M; m++) {
-            const uint32_t p = p0 + m;
-            if (p + 1u >= W && p < L) {
-                const uint32_t i = p + 1u - W;
-                if (mo) mo[i] = U[m];
-                if (U[m] > best) { best = U[m]; best_i = i; }
-            }
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {                  // first arg-max over the wave
-            const float ob = __shfl_xor(best, o, 64);
-            const uint32_t oi = __shfl_xor(best_i, o, 64);
-            const bool take = (ob > best) || (ob == best && oi < best_i);
-            best = take ? ob : best;
-            best_i = take ? oi : best_i;
-        }
-        if (lane == 0) { a.zoops[seq] = best; a.z[seq] = best_i; }
-    }
-}
-
-
 template <int M, int THREADS>
 int launch_em_variant(bool accum, bool write_r, const EmKernelArgs& a, uint32_t blocks, uint32_t threads,
                       size_t lds, hipStream_t st) {
@@ -794,25 +735,6 @@ uint32_t pick_log_copies(uint32_t W, uint32_t Y, uint32_t blocks_per_cu, size_t 
     while (logC < 4 && em_lds_bytes(W, Y, true, logC + 1, scratch) <= budget) logC++;
     return logC;
 }
-
-#define BAMM_FOR_EACH_MCLASS(X) \
-    X(0, 1, 1024) X(1, 2, 1024) X(2, 3, 1024) X(3, 4, 1024) X(4, 5, 1024) X(5, 6, 1024) X(6, 7, 1024) \
-    X(7, 8, 1024) X(8, 10, 768) X(9, 12, 768) X(10, 14, 768) X(11, 16, 768) X(12, 20, 768)             \
-    X(13, 24, 512) X(14, 28, 512) X(15, 32, 512) X(16, 40, 512) X(17, 48, 512) X(18, 56, 512) X(19, 64, 512) \
-    X(20, 80, 256) X(21, 96, 256) X(22, 128, 256)
-
-namespace {
-// f(M, THREADS) with the class's values as std::integral_constant arguments
-template <class F>
-int with_mclass(int mclass, F&& f) {
-    switch (mclass) {
-#define X(idx, M, T) case idx: return f(std::integral_constant<int, M>(), std::integral_constant<int, T>());
-        BAMM_FOR_EACH_MCLASS(X)
-#undef X
-        default: set_error("no kernel for M class %d", mclass); return BAMM_ERR_UNSUPPORTED;
-    }
-}
-}  // namespace
 
 int launch_em_seq(int mclass, bool accum, bool write_r, const EmKernelArgs& a, uint32_t blocks,
                   uint32_t threads, hipStream_t st) {
@@ -880,22 +802,5 @@ int launch_m_list(int mclass, const EmKernelArgs& a, uint32_t j0, uint32_t j1, u
     BAMM_HIP(hipGetLastError());
     return BAMM_OK;
 }
-
-int launch_score(int mclass, const ScoreKernelArgs& a, uint32_t blocks, uint32_t threads, hipStream_t st) {
-    const size_t lds = (size_t)a.W * (a.Y + 1) * sizeof(float);
-    if (lds > 160 * 1024) {
-        set_error("log-odds table needs %zu bytes of LDS (> 160 KiB)", lds);
-        return BAMM_ERR_UNSUPPORTED;
-    }
-    if (threads > max_threads_for_mclass(mclass) || (threads & 63u) || threads == 0 || blocks == 0) {
-        set_error("bad launch geometry %u x %u for M class %d", blocks, threads, mclass);
-        return BAMM_ERR_ARG;
-    }
-    if (int rc = with_mclass(mclass, [&](auto M, auto T) { return launch_kernel(&k_score<M, T>, blocks, threads, lds, st, a); }))
-        return rc;
-    BAMM_HIP(hipGetLastError());
-    return BAMM_OK;
-}
-
 
 }  // namespace bamm

@@ -6,7 +6,7 @@
 //   k_long_score  ScoreSeqSet::calcLogOdds  seq_scoring/ScoreSeqSet.cpp:41-66 -- the scorer of the log-odds tables
 //                 beyond the LDS (any length then) and of long records under bamm_ctx_set_tuning("score_tiles", 0);
 //                 while the table fits the LDS, long records are scored tile by tile on the whole GPU instead
-//                 (score_tile.hip; score.cpp: score_route)
+//                 (scorer.hip; score.cpp: score_route)
 //
 // The reference has no length limit (init/Sequence.cpp:4-43); the fast kernels hold a sequence in the
 // registers of one wavefront.  Records this long are rare in motif discovery (ChIP-seq peaks are a few
@@ -49,9 +49,8 @@ __device__ __forceinline__ uint32_t kmer_at(const LongSeq& s, uint32_t p, uint32
         if (s.exc[mid].x < p) lo = mid + 1u; else hi = mid;
     }
     if (lo < s.n_exc && s.exc[lo].x == p) return s.exc[lo].y;
-    const uint32_t wi = p >> 4;
-    const uint32_t w_lo = s.words[wi], w_hi = wi ? s.words[wi - 1u] : 0u;
-    return __builtin_amdgcn_alignbit(w_hi, w_lo, 30u - 2u * (p & 15u)) & (Y - 1u);
+    const uint32_t* wp = s.words;                          // (a local, not s.words in the call: k_long_em's instructions stay what they were)
+    return stream_kmer(wp, p, Y);
 }
 
 // product of window i (EM.cpp:167-176): columns j with i+j < LW1 only (the reference's loop bound)
@@ -137,14 +136,9 @@ __global__ void __launch_bounds__(256) k_long_score(ScoreKernelArgs a) {
             if (mo) mo[i] = sc;
             if (sc > best) { best = sc; best_i = i; }       // ascending i per thread: the first maximum stays
         }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {                  // first arg-max over the wave, then over the four waves
-            const float ob = __shfl_xor(best, o, 64);
-            const uint32_t oi = __shfl_xor(best_i, o, 64);
-            const bool take = (ob > best) || (ob == best && oi < best_i);
-            best = take ? ob : best;
-            best_i = take ? oi : best_i;
-        }
+        const WaveMax wm = wave_first_max(best, best_i);   // over the wave, then over the four waves
+        best = wm.best;
+        best_i = wm.best_i;
         __syncthreads();
         if ((threadIdx.x & 63u) == 0u) { sbest[threadIdx.x >> 6] = best; sidx[threadIdx.x >> 6] = best_i; }
         __syncthreads();

@@ -18,7 +18,7 @@
 // LDS array once and addressed at random from there.  Only ~f of the windows do work per
 // iteration, so none of this is on the headline path: simplicity over the last factor of two.
 
-#include "common.h"
+#include "device_utils.h"
 
 #include <algorithm>
 #include <type_traits>
@@ -26,29 +26,15 @@
 namespace bamm {
 namespace {
 
-__device__ __forceinline__ void wave_lds_sync() {
-    // DS operations of one wave retire in order; this only stops the compiler from moving LDS
-    // reads above the writes of other lanes
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-__device__ __forceinline__ void acc_add(long long* cell, long long v) {      // as device_utils.h:acc_add
-    (void)__hip_atomic_fetch_add(cell, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// as device_utils.h: a sequence's statistics rounded to the accumulator's units before they are summed (exact sums)
-__device__ __forceinline__ double stat_round_llh(double x) { return (x + 402653184.0) - 402653184.0; }      // 1.5 * 2^28
-__device__ __forceinline__ double stat_round_sumr(double x) { return (x + 6291456.0) - 6291456.0; }          // 1.5 * 2^22
-
+// not device_utils.h's wave_sum (a DPP row sum): a butterfly adds in another order, and the bits differ
 __device__ __forceinline__ float mask_wave_sum(float x) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
     return x;
 }
 
-__device__ __forceinline__ unsigned long long mask_to_fixed40(float r) {   // as kernels.hip:to_fixed40
+// not device_utils.h's to_fixed40 (v_fract_f32): floorf and a subtraction are the arithmetic EM::mask's counts were made with
+__device__ __forceinline__ unsigned long long mask_to_fixed40(float r) {
     const float a = r * 256.0f;
     const float hi_f = floorf(a);
     const uint32_t hi = (uint32_t)hi_f;
@@ -84,24 +70,6 @@ template <bool WG>
 __device__ __forceinline__ WaveLds<WG> wave_arrays(unsigned char* lds_base, const MaskKernelArgs& a, uint32_t wave, uint32_t wpb) {
     if constexpr (WG) return wave_lds<true>(a.wave_scratch, a, (uint64_t)blockIdx.x * wpb + wave);
     else return wave_lds<false>(lds_base, a, wave);
-}
-
-// kmer_[p] mod Y for every position of one sequence (Sequence.cpp:35-41) into LDS
-__device__ __forceinline__ void decode_to_lds(const SeqView& sv, uint32_t seq, uint32_t L, uint32_t Y, int lane,
-                                              uint32_t* ybuf) {
-    const uint32_t* wp = sv.words + sv.word_off[seq];
-    for (uint32_t p = (uint32_t)lane; p < L; p += 64u) {
-        const uint32_t wi = p >> 4;
-        const uint32_t lo = wp[wi], hi = wi ? wp[wi - 1u] : 0u;
-        ybuf[p] = __builtin_amdgcn_alignbit(hi, lo, 30u - 2u * (p & 15u)) & (Y - 1u);
-    }
-    wave_lds_sync();
-    const uint64_t e0 = sv.exc_off[seq], e1 = sv.exc_off[seq + 1];
-    for (uint64_t e = e0 + (uint64_t)lane; e < e1; e += 64u) {       // N randomisation (Sequence.cpp:38)
-        const uint2 x = sv.exc[e];
-        if (x.x < L) ybuf[x.x] = x.y;
-    }
-    wave_lds_sync();
 }
 
 // the membership words of this sequence's r slots, then the listed r-indices in ascending order

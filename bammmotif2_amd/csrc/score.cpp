@@ -13,7 +13,7 @@ namespace bamm {
 namespace {
 
 // The scorer a length bucket takes: k_score while a sequence fits one wavefront's registers, beyond that the same chain
-// tile by tile (score_tile.hip) -- both with the log-odds table in LDS --, and the window-by-window scorer (long_seq.hip),
+// tile by tile (both in scorer.hip, one chain, the log-odds table in LDS), and the window-by-window scorer (long_seq.hip),
 // which reads the table from global memory, for tables beyond the LDS of a CU (orders >= 6 at usual widths), for widths
 // that leave a tile no stride, and for long sequences under bamm_ctx_set_tuning("score_tiles", 0).
 enum class ScoreRoute { kWave, kTiles, kWindows };

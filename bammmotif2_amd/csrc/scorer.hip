@@ -1,29 +1,33 @@
-// Long sequences through the register-resident scorer, tile by tile.
+// The log-odds scorer with the table in LDS: ScoreSeqSet::calcLogOdds, seq_scoring/ScoreSeqSet.cpp:41-66.
 //
-//   k_score_tile         ScoreSeqSet::calcLogOdds seq_scoring/ScoreSeqSet.cpp:41-66 over one tile of one long sequence
-//   k_score_tile_reduce  the sequence's maximum (ScoreSeqSet.cpp:46-57) over its tiles
+//   k_score              one wavefront per sequence of a length class (up to 8192 positions)
+//   k_score_tile         the same over one tile of one longer sequence
+//   k_score_tile_reduce  that sequence's maximum (ScoreSeqSet.cpp:46-57) over its tiles
 //
 // A window's score is W additions, left to right, of table entries picked by the k-mers inside the window: it depends on
-// nothing else in the sequence.  So a sequence beyond the length classes (more than 8192 positions) is cut into tiles of
-// 64 * M positions that overlap by at least W - 1, and a wavefront runs on one tile the chain k_score (kernels.hip) runs
-// on one short sequence: the same LDS table [W][Y+1], the same U[m] = U[m-1] + sj[y[m]] with wave_shr1 across lanes --
-// the same sums in the same order, bit for bit what k_long_score (long_seq.hip) and the reference give.  A tile starts on a
-// multiple of the stride, the stride is a multiple of 16 (a tile starts on a word of the 2-bit stream) and at most
-// 64 * M - (W - 1); a tile emits the windows that start in [t0, t0 + stride), the sequence's last tile up to L - W.
+// nothing else in the sequence.  Lane l holds M consecutive positions in registers, the table lives in LDS as [W][Y+1]
+// (row Y = 0.0f), and the window sums are a systolic chain whose only cross-lane traffic is one wave_shr1 per motif
+// column.  That chain exists once, in score_chain, and so does the wave's first arg-max (wave_first_max, device_utils.h):
+// both kernels load the table, pick a sequence or a tile, decode it, run score_chain, emit their windows and fold the
+// maximum -- so every route adds the same numbers in the same order, bit for bit what k_long_score (long_seq.hip) and
+// the reference give.
 //
-// A tile is found from its index: the launch carries the prefix sums of the bucket's tile counts, one entry per long
-// sequence, and a wave searches them.  A sequence the mask leaves out has no tiles.
+// Tiles: a sequence beyond the length classes is cut into tiles of 64 * M positions that overlap by at least W - 1.  A
+// tile starts on a multiple of the stride, the stride is a multiple of 16 (a tile starts on a word of the 2-bit stream)
+// and at most 64 * M - (W - 1); a tile emits the windows that start in [t0, t0 + stride), the sequence's last tile up to
+// L - W.  A tile is found from its index: the launch carries the prefix sums of the bucket's tile counts, one entry per
+// long sequence, and a wave searches them.  A sequence the mask leaves out has no tiles.  Every tile leaves (best, first
+// window that reaches it), the reduction folds a sequence's tiles with the scorer's rule (strict >, the lowest index
+// among equals) -- no float atomics, nothing that depends on scheduling.
 //
-// The maximum: every tile leaves (best, first window that reaches it), the reduction folds a sequence's tiles with the
-// scorer's rule (strict >, the lowest index among equals) -- no float atomics, nothing that depends on scheduling.
-//
-// This unit is compiled with the flags of kernels.hip's scorer (no contraction, no fast math): the additions are IEEE fp32.
+// No contraction, no fast math (build.py): the additions are IEEE fp32.
 #include "device_utils.h"
+#include "mclass.h"
 
 #include <algorithm>
 #include <cfloat>
 
-// The one geometry (positions per lane, threads per block: a class of BAMM_FOR_EACH_MCLASS in kernels.hip), chosen by
+// The tiles' one geometry (positions per lane, threads per block: a class of BAMM_FOR_EACH_MCLASS, mclass.h), chosen by
 // measurement (profiles/score_tiles_ab.txt).  tools/score_tiles_ab.py builds the other candidates by overriding the two.
 #ifndef BAMM_SCORE_TILE_M
 #define BAMM_SCORE_TILE_M 32
@@ -42,7 +46,10 @@ static_assert(kTileThreads % 64 == 0 && kTileThreads <= 1024, "whole waves");
 // position's k-mer reaches up to K <= 10 bases back); it is zero at the start of a sequence.  Of the sequence's
 // exceptions only those inside the tile are visited: one binary search for the first, then the run up to the tile's end
 // -- never the whole list, which holds millions of entries for a chromosome.  (Kept apart from decode_positions so that
-// the kernels built on that one compile to what they did.)
+// the kernels built on that one compile to what they did.  Moving only the unpack loop that decode_positions and
+// decode_raw share into one forceinline helper changed the instructions of 114 of the 163 kernels of kernels.hip --
+// k_em_seq<64,false,false,512> 4035 -> 3526, k_m_slice<32,512> 10189 -> 10236, k_m_list<64,512> 256 -> 191 VGPRs --
+// none of which has been timed: this unpack loop stays a copy until somebody measures those.)
 template <int M>
 __device__ __forceinline__ void decode_tile(const SeqView& sv, uint32_t seq, uint32_t L, uint32_t Y, uint32_t t0, int lane,
                                             uint32_t (&y)[M]) {
@@ -101,13 +108,76 @@ __device__ __forceinline__ uint32_t tile_owner(const uint32_t* tile_off, uint32_
     return lo;
 }
 
+// The scoring chain, once.  y[m]: the k-mer at position lane * M + m of the sequence or tile the wave holds; s_lds: the
+// table [W][Ys].  After column j, U[m] is the sum of columns 0..j of the window that ends j columns further on: W
+// additions per window, left to right (ScoreSeqSet.cpp:49-54; 0.0f + s == s).  Slot p = lane * M + m is left holding the
+// score of window i = p + 1 - W.
+// (The emit loops behind it stay with their kernels.  In one function with the chain, every spelling of the emit guard
+// tried cost one of the two callers: `p < end` is the compare k_score's decode makes too and keeps its 23 classes'
+// registers, but k_score_tile<32, 512> then needs 149 VGPRs instead of 118 and loses a wave per SIMD; `i < n_emit` keeps
+// the tile kernel's and puts more scratch into k_score<56> and <64>.  profiles/scorer_refactor_isa.txt)
+template <int M>
+__device__ __forceinline__ void score_chain(const uint32_t (&y)[M], const float* s_lds, uint32_t W, uint32_t Ys, float (&U)[M]) {
+    const float* sj = s_lds;
+#pragma unroll
+    for (int m = 0; m < M; m++) U[m] = sj[y[m]];
+    for (uint32_t j = 1; j < W; j++) {
+        sj += Ys;
+        const float carry = wave_shr1(0.0f, U[M - 1]);
+#pragma unroll
+        for (int m = M - 1; m >= 1; m--) U[m] = U[m - 1] + sj[y[m]];
+        U[0] = carry + sj[y[0]];
+    }
+}
+
+// the block's copy of the log-odds table
+__device__ __forceinline__ void load_table(float* s_lds, const float* s, uint32_t cells) {
+    for (uint32_t i = threadIdx.x; i < cells; i += blockDim.x) s_lds[i] = s[i];
+    __syncthreads();
+}
+
+template <int M, int THREADS>
+__global__ void __launch_bounds__(THREADS) k_score(ScoreKernelArgs a) {
+    extern __shared__ float lds[];
+    const uint32_t W = a.W, Ys = a.Y + 1u;
+    load_table(lds, a.s, W * Ys);
+
+    const int lane = threadIdx.x & 63;
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint32_t waves_per_block = blockDim.x >> 6;
+    const uint32_t total_waves = gridDim.x * waves_per_block;
+
+    for (uint32_t t = blockIdx.x * waves_per_block + wave; t < a.sv.count; t += total_waves) {
+        const uint32_t seq = pick_sequence(a.sv, t);
+        if (a.sv.mask && !a.sv.mask[seq]) continue;
+        const uint32_t L = a.sv.len[seq];
+        uint32_t y[M];
+        decode_positions<M>(a.sv, seq, L, a.Y, L, lane, y);   // full windows (ScoreSeqSet.cpp:49-54)
+        const uint32_t p0 = (uint32_t)lane * M;
+        float U[M];
+        score_chain<M>(y, lds, W, Ys, U);
+        float best = -FLT_MAX;                              // ScoreSeqSet.cpp:46
+        uint32_t best_i = 0;
+        float* mo = a.mops ? a.mops + a.mops_off[seq] : nullptr;
+#pragma unroll
+        for (int m = 0; m < M; m++) {
+            const uint32_t p = p0 + m;
+            if (p + 1u >= W && p < L) {                     // every window of the sequence
+                const uint32_t i = p + 1u - W;
+                if (mo) mo[i] = U[m];
+                if (U[m] > best) { best = U[m]; best_i = i; }   // ascending i per lane: the first maximum stays
+            }
+        }
+        const WaveMax r = wave_first_max(best, best_i);
+        if (lane == 0) { a.zoops[seq] = r.best; a.z[seq] = r.best_i; }
+    }
+}
+
 template <int M, int THREADS>
 __global__ void __launch_bounds__(THREADS) k_score_tile(ScoreTileArgs a) {
     extern __shared__ float lds[];
-    const uint32_t W = a.k.W, Y = a.k.Y, Ys = a.k.Y + 1u;
-    float* s_lds = lds;                                  // [W][Y+1], row Y = 0.0f
-    for (uint32_t i = threadIdx.x; i < W * Ys; i += blockDim.x) s_lds[i] = a.k.s[i];
-    __syncthreads();
+    const uint32_t W = a.k.W, Ys = a.k.Y + 1u;
+    load_table(lds, a.k.s, W * Ys);
 
     const int lane = threadIdx.x & 63;
     const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -120,22 +190,12 @@ __global__ void __launch_bounds__(THREADS) k_score_tile(ScoreTileArgs a) {
         const uint32_t L = a.k.sv.len[seq];
         const uint32_t t0 = (g - a.tile_off[t]) * a.stride;
         const uint32_t n_emit = min(a.stride, L - W + 1u - t0);   // windows t0 .. t0 + n_emit - 1 are this tile's
-        const uint32_t p0 = (uint32_t)lane * M;
         uint32_t y[M];
-        decode_tile<M>(a.k.sv, seq, L, Y, t0, lane, y);
-
-        float U[M];                                          // k_score's chain (kernels.hip), on the tile
-        const float* sj = s_lds;
-#pragma unroll
-        for (int m = 0; m < M; m++) U[m] = sj[y[m]];        // 0.0f + s == s
-        for (uint32_t j = 1; j < W; j++) {
-            sj += Ys;
-            const float carry = wave_shr1(0.0f, U[M - 1]);
-#pragma unroll
-            for (int m = M - 1; m >= 1; m--) U[m] = U[m - 1] + sj[y[m]];
-            U[0] = carry + sj[y[0]];
-        }
-        float best = -FLT_MAX;                              // ScoreSeqSet.cpp:46
+        decode_tile<M>(a.k.sv, seq, L, a.k.Y, t0, lane, y);
+        const uint32_t p0 = (uint32_t)lane * M;
+        float U[M];
+        score_chain<M>(y, lds, W, Ys, U);
+        float best = -FLT_MAX;
         uint32_t best_i = 0;
         float* mo = a.k.mops ? a.k.mops + a.k.mops_off[seq] + t0 : nullptr;
 #pragma unroll
@@ -147,15 +207,8 @@ __global__ void __launch_bounds__(THREADS) k_score_tile(ScoreTileArgs a) {
                 if (U[m] > best) { best = U[m]; best_i = t0 + i; }
             }
         }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {                  // first arg-max over the wave
-            const float ob = __shfl_xor(best, o, 64);
-            const uint32_t oi = __shfl_xor(best_i, o, 64);
-            const bool take = (ob > best) || (ob == best && oi < best_i);
-            best = take ? ob : best;
-            best_i = take ? oi : best_i;
-        }
-        if (lane == 0) { a.tile_best[g] = best; a.tile_idx[g] = best_i; }
+        const WaveMax r = wave_first_max(best, best_i);
+        if (lane == 0) { a.tile_best[g] = r.best; a.tile_idx[g] = r.best_i; }
     }
 }
 
@@ -173,23 +226,32 @@ __global__ void __launch_bounds__(256) k_score_tile_reduce(ScoreTileArgs a) {
             const float b = a.tile_best[g];
             if (b > best) { best = b; best_i = a.tile_idx[g]; }
         }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const float ob = __shfl_xor(best, o, 64);
-            const uint32_t oi = __shfl_xor(best_i, o, 64);
-            const bool take = (ob > best) || (ob == best && oi < best_i);
-            best = take ? ob : best;
-            best_i = take ? oi : best_i;
-        }
+        const WaveMax r = wave_first_max(best, best_i);
         if (lane == 0) {
             const uint32_t seq = pick_sequence(a.k.sv, t);
-            a.k.zoops[seq] = best;
-            a.k.z[seq] = best_i;
+            a.k.zoops[seq] = r.best;
+            a.k.z[seq] = r.best_i;
         }
     }
 }
 
 }  // namespace
+
+int launch_score(int mclass, const ScoreKernelArgs& a, uint32_t blocks, uint32_t threads, hipStream_t st) {
+    const size_t lds = (size_t)a.W * (a.Y + 1) * sizeof(float);
+    if (lds > 160 * 1024) {
+        set_error("log-odds table needs %zu bytes of LDS (> 160 KiB)", lds);
+        return BAMM_ERR_UNSUPPORTED;
+    }
+    if (threads > max_threads_for_mclass(mclass) || (threads & 63u) || threads == 0 || blocks == 0) {
+        set_error("bad launch geometry %u x %u for M class %d", blocks, threads, mclass);
+        return BAMM_ERR_ARG;
+    }
+    if (int rc = with_mclass(mclass, [&](auto M, auto T) { return launch_kernel(&k_score<M, T>, blocks, threads, lds, st, a); }))
+        return rc;
+    BAMM_HIP(hipGetLastError());
+    return BAMM_OK;
+}
 
 bool score_tile_geometry(uint32_t W, uint32_t* tile_positions, uint32_t* stride) {
     if (W == 0 || W > kTilePositions) return false;

@@ -29,12 +29,6 @@
 namespace bamm {
 namespace {
 
-__device__ __forceinline__ void seed_lds_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 template <bool WG>
 __global__ void __launch_bounds__(1024) k_seed_pwm(SeedKernelArgs a) {
     extern __shared__ __align__(16) unsigned char smem[];
@@ -67,21 +61,7 @@ __global__ void __launch_bounds__(1024) k_seed_pwm(SeedKernelArgs a) {
         if (L < W) { if (lane == 0 && a.z_out) a.z_out[seq] = 0u; continue; }          // Motif.cpp:240-248
         const uint32_t LW1 = L - W + 1u;
         // kmer_[p] mod 4^(K+1) for every position (Sequence.cpp:35-41), N exceptions applied
-        {
-            const uint32_t* wp = a.sv.words + a.sv.word_off[seq];
-            for (uint32_t p = (uint32_t)lane; p < L; p += 64u) {
-                const uint32_t wi = p >> 4;
-                const uint32_t lo = wp[wi], hi = wi ? wp[wi - 1u] : 0u;
-                ybuf[p] = __builtin_amdgcn_alignbit(hi, lo, 30u - 2u * (p & 15u)) & (Y - 1u);
-            }
-            seed_lds_sync();
-            const uint64_t e0 = a.sv.exc_off[seq], e1 = a.sv.exc_off[seq + 1];
-            for (uint64_t e = e0 + (uint64_t)lane; e < e1; e += 64u) {
-                const uint2 x = a.sv.exc[e];
-                if (x.x < L) ybuf[x.x] = x.y;
-            }
-            seed_lds_sync();
-        }
+        decode_to_lds(a.sv, seq, L, Y, lane, ybuf);
         // window products, Motif.cpp:277-287 (same multiplication order; digit 0 of the k-mer is the base)
         const float pos1 = a.q / (float)LW1;
         for (uint32_t i = (uint32_t)lane; i < LW1; i += 64u) {
@@ -90,7 +70,7 @@ __global__ void __launch_bounds__(1024) k_seed_pwm(SeedKernelArgs a) {
             rf[i + 1u] = r * pos1;
         }
         if (lane == 0) rf[0] = pos0;
-        seed_lds_sync();
+        wave_lds_sync();
         float nf = 0.0f;
         if (lane == 0) {                                     // sequential fp32 sum, then + (1-q)  (:285,290)
             uint32_t i = 1;
@@ -100,7 +80,7 @@ __global__ void __launch_bounds__(1024) k_seed_pwm(SeedKernelArgs a) {
         }
         nf = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, nf)));
         for (uint32_t i = (uint32_t)lane; i <= LW1; i += 64u) rf[i] = rf[i] / nf;       // :292-294
-        seed_lds_sync();
+        wave_lds_sync();
         double sum = 0.0;
         if (lane == 0) {                                     // std::accumulate(begin, end, 0.0)
             uint32_t i = 0;
@@ -115,7 +95,7 @@ __global__ void __launch_bounds__(1024) k_seed_pwm(SeedKernelArgs a) {
             sum = __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
         }
         for (uint32_t i = (uint32_t)lane; i <= LW1; i += 64u) pd[i] = (double)rf[i] / sum;   // __normalize
-        seed_lds_sync();
+        wave_lds_sync();
         uint32_t z = LW1;                                    // cp[LW1] is forced to 1.0 and u < 1
         if (lane == 0) {
             const double u = a.u[seq];
@@ -139,7 +119,7 @@ __global__ void __launch_bounds__(1024) k_seed_pwm(SeedKernelArgs a) {
                 }
             }
         }
-        seed_lds_sync();
+        wave_lds_sync();
     }
     __syncthreads();
     if (cnt_lds)

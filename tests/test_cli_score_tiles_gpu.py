@@ -1,5 +1,5 @@
 """`BaMMmotif ... --scoreSeqset` on a FASTA with one record of 20 kb among 50 of 200 bp: the long record is scored tile by
-tile (csrc/score_tile.hip) by default and window by window with BAMM_NO_SCORE_TILES=1 in the environment -- the driver's
+tile (csrc/scorer.hip, the one score_chain k_score runs too) by default and window by window with BAMM_NO_SCORE_TILES=1 in the environment -- the driver's
 switch for comparing the program with itself.  Every output file, the .occurrence listing first, byte for byte."""
 import os
 import random

@@ -1,4 +1,4 @@
-"""The tiles the scorer cuts a long sequence into (bamm_score_tile_geometry, csrc/score_tile.hip): a tile of
+"""The tiles the scorer cuts a long sequence into (bamm_score_tile_geometry, csrc/scorer.hip): a tile of
 tile_positions positions starts on a multiple of the stride and emits the windows that start in its first `stride`
 positions, the last tile up to L - W.  Pure host arithmetic: no device."""
 import numpy as np

@@ -1,4 +1,4 @@
-"""Sequences beyond 8192 positions through the scorer tile by tile (csrc/score_tile.hip: k_score_tile): every case is
+"""Sequences beyond 8192 positions through the scorer tile by tile (csrc/scorer.hip: k_score_tile, which runs the one score_chain that k_score runs): every case is
 scored three ways -- the tiles, the same context with score_tiles=0 (the window-by-window scorer of long_seq.hip) and the
 CPU oracle's log-odds -- and mops, zoops and z must be equal element for element.  Tile size and stride come from
 bamm_score_tile_geometry; the cases put N, strand junctions, sequence ends and equal maxima on the tile boundaries.
