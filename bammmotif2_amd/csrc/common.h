@@ -257,9 +257,11 @@ int launch_em_grp_xl(int mclass, bool accum, bool write_r, const GrpKernelArgs& 
 uint32_t grp_max_threads(int M);   // block size the grouped kernel of this length class is built for
 // mixed rows: geometry (false: does not apply / does not fit) and the launchers of its two translation units
 bool mix_geometry(uint32_t K, uint32_t W, int M, uint32_t waves, bool accum, GrpGeom* out);
-// mixed rows, accumulating layout: the motif's leading columns whose bins [j][y] are resident in LDS (K = 2: 64 bins of 8 bytes);
-// the fix lanes add to those and log the other columns' sums -- the kernel and the builder of the lane records agree through this
-inline __host__ __device__ uint32_t mix_resident_cols(const GrpGeom& g) { return g.wave_bytes / (64u * 8u); }
+// mixed rows, accumulating layout: the motif's leading columns whose bins [j][y] are resident in LDS (K = 2: 64 bins of 8 bytes
+// and a 65th cell that takes the adds of the code "no bin"); the fix lanes add to those and log the other columns' sums -- the
+// kernel and the builder of the lane records agree through this
+constexpr uint32_t kMixBinBytes = 65u * 8u;
+inline __host__ __device__ uint32_t mix_resident_cols(const GrpGeom& g) { return g.wave_bytes / kMixBinBytes; }
 int launch_em_mix(int mclass, bool accum, bool write_r, const GrpKernelArgs& a, uint32_t blocks, uint32_t threads, hipStream_t st);
 int launch_em_mix1(int mclass, bool accum, bool write_r, const GrpKernelArgs& a, uint32_t blocks, uint32_t threads, hipStream_t st);
 int launch_em_grp(int mclass, bool accum, bool write_r, const GrpKernelArgs& a, uint32_t blocks, uint32_t threads,

@@ -52,12 +52,13 @@ bool mix_geometry(uint32_t K, uint32_t W, int M, uint32_t waves, bool accum, Grp
         const uint32_t counts = accum ? up16(A * R6T * 8u) + up16(B * g.Rtot * 8u) : 0u;
         g.off_ng = off + (accum ? up16(A * R6T * 8u) : 0u);
         off += std::max(counts, up16(W * (Y + 1u) * 4u));
-        // resident bins for as many of the motif's leading columns as fit (the fix lanes log the rest)
+        // resident bins for as many of the motif's leading columns as fit (the fix lanes log the rest): Y + 1 cells per
+        // column, the last one for the code "no bin" (mixed_kernel.h)
         g.off_wave = off;
         g.wave_bytes = 0u;
         if (accum && off <= 160u * 1024u) {
-            const uint32_t cols = std::min(W, (160u * 1024u - off) / (Y * 8u));
-            g.wave_bytes = cols * Y * 8u;
+            const uint32_t cols = std::min(W, (160u * 1024u - off) / kMixBinBytes);
+            g.wave_bytes = cols * kMixBinBytes;
             off += g.wave_bytes;
         }
         g.cap = 0u;                                          // the single-column table is not resident

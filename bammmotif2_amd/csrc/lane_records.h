@@ -7,7 +7,7 @@
 // One uint2 per (launch slot t of the bucket, lane), 512 bytes per sequence, read as one coalesced 8-byte load per lane:
 //   x = the lane's stream window (it ends at the lane's last position) in bits 0..30 -- the rows of M <= 10 positions
 //       take 2 (M - 1) + 12 <= 30 of them --, bit 31 = the lane IS a fix lane of this sequence (it rewrites its virtual
-//       odds cell and clears its virtual count cell even when every field is Y: the wave's previous sequence left both
+//       odds cell and reads its virtual count cell even when every field is Y: the wave's previous sequence left both
 //       behind); the flag rides in the word whose every other use masks it out
 //   y = the y of the fix lane's up to four columns, 7 bits each (Y = 64: none; bits 28..30 stay 0), bit 31 = something
 //       is LEFT TO LOG: some column of the lane has a y and no resident bin (mix_fix_word: the layout's n1c leading

@@ -50,6 +50,15 @@ __device__ __forceinline__ void mix_rows(uint32_t X, int at, uint32_t special, u
     row5_biased = max(six | kMixRow5Bias, special);
 }
 
+// a 64-bit LDS cell by its byte address: a plain load, the compiler's to schedule and wait for
+__device__ __forceinline__ unsigned long long lds_read_u64(uint32_t byte_addr) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return *(const __attribute__((address_space(3))) unsigned long long*)(size_t)byte_addr;
+#else
+    return 0ull;
+#endif
+}
+
 template <int OFF>
 __device__ __forceinline__ void lds_add_u64_exec_big(uint32_t byte_addr, unsigned long long v, unsigned long long mask) {
     static_assert(OFF >= 0 && OFF < 65536, "ds offset field");
@@ -64,6 +73,7 @@ __global__ void __launch_bounds__(THREADS) k_em_mix(GrpKernelArgs ga) {
     constexpr uint32_t R5N = 1024u, R5V0 = R5N + 1u, R5T = R5V0 + V;          // neutral row, first virtual row, rows
     constexpr uint32_t R6N = 4096u, R6V0 = R6N + 1u, R6T = R6V0 + V;
     constexpr uint32_t Y = 64u, Ys = 65u;                      // K = 2
+    static_assert(Ys * 8u == kMixBinBytes, "a resident column's bins and its dump cell (mix_geometry)");
     if (ga.e.stop != nullptr && *ga.e.stop != 0u) return;    // optimize(): the stop rule fired in an earlier pass
     extern __shared__ __align__(16) unsigned char lds_raw[];
     BAMM_PHASE(0);
@@ -86,7 +96,9 @@ __global__ void __launch_bounds__(THREADS) k_em_mix(GrpKernelArgs ga) {
     unsigned long long* n1 = reinterpret_cast<unsigned long long*>(lds_raw + g.off_n1);   // epilogue only: over sg6
     // bins [j][y] of the motif's first n1c columns, resident: what the fix lanes take out of their virtual count rows
     // for those columns is added here; only the other columns' sums go through the log (each logged entry costs a
-    // store request in the loop and a read in the epilogue: all of them 0.875 ms, a third of them 0.814 ms)
+    // store request in the loop and a read in the epilogue: all of them 0.875 ms, a third of them 0.814 ms).
+    // Ys = Y + 1 cells per column: the code Y ("no bin": neutral, beyond the edge) lands in a dump cell nobody reads, so
+    // a lane's add needs no compare of its code -- the sum a fix lane holds goes to the cell of every resident column's code
     unsigned long long* n1p = reinterpret_cast<unsigned long long*>(lds_raw + g.off_wave);
     const uint32_t n1c = ACCUM ? mix_resident_cols(g) : 0u;
 
@@ -149,7 +161,7 @@ __global__ void __launch_bounds__(THREADS) k_em_mix(GrpKernelArgs ga) {
         if (ACCUM) {                                         // the staging area becomes the count tables
             for (uint32_t i = threadIdx.x; i < B * R5T; i += THREADS) cnt5[i] = 0ull;
             for (uint32_t i = threadIdx.x; i < A * R6T; i += THREADS) cnt6[i] = 0ull;
-            for (uint32_t i = threadIdx.x; i < n1c * Y; i += THREADS) n1p[i] = 0ull;
+            for (uint32_t i = threadIdx.x; i < n1c * Ys; i += THREADS) n1p[i] = 0ull;
             __syncthreads();
         }
     }
@@ -197,7 +209,13 @@ __global__ void __launch_bounds__(THREADS) k_em_mix(GrpKernelArgs ga) {
     const uint32_t fix_s1 = __umul24(lane_col0, Ys * 4u);
     // the lane's virtual odds cell, in whichever table its group is: one address, one write per sequence for narrow and wide lanes alike
     float* const fix_odds = lane_wide ? sg6 + ((vbase6 + lane_b) * A + (lane_t - B)) : sg5 + (__umul24(vbase5 + lane_b, rs5) + pad + lane_t);
-    [[maybe_unused]] const uint32_t fix_bin = lds_offset(n1p) + lane_col0 * (Y * 8u);
+    [[maybe_unused]] const uint32_t fix_bin = lds_offset(n1p) + lane_col0 * (Ys * 8u);
+    // the lane's virtual count cell, its own for the whole launch, and the total it held when the lane last looked: the cell is
+    // never cleared (a ds_write_b64 per sequence); what one sequence's window added is the difference of two totals, exact
+    // in 64-bit modular arithmetic.  The prologue zeroed the cell; the epilogue reads table rows only, never a virtual one.
+    [[maybe_unused]] const uint32_t fix_cell = lds_offset(lane_wide ? cnt6 + (size_t)(T - 1u - lane_t) * R6T + vbase6 + lane_b
+                                                                    : cnt5 + (size_t)(B - 1u - lane_t) * R5T + vbase5 + lane_b);
+    [[maybe_unused]] unsigned long long fix_total = 0ull;
     double llh_acc = 0.0, sumr_acc = 0.0;
     uint32_t seq_cnt = 0, last_LW1 = 0;
     float pos_i = 0.0f;
@@ -414,20 +432,20 @@ __global__ void __launch_bounds__(THREADS) k_em_mix(GrpKernelArgs ga) {
             wave_lds_sync();
             unsigned long long acc = 0ull;
             if (fix) {
-                unsigned long long* cell = lane_wide ? cnt6 + (size_t)(T - 1u - lane_t) * R6T + vbase6 + lane_b
-                                                     : cnt5 + (size_t)(B - 1u - lane_t) * R5T + vbase5 + lane_b;
-                acc = *cell;
-                *cell = 0ull;
+                const unsigned long long now = lds_read_u64(fix_cell);
+                acc = now - fix_total;
+                fix_total = now;
             }
             // code: group (3 bits), then the y of its up to four columns (7 bits each, >= Y = nothing to log: neutral,
             // beyond the edge, or a resident bin, which takes the sum here)
             // (fields of columns beyond the lane's group hold Y already: yfix is built that way)
-            // a column with a y and a resident bin: added here, not logged.  The lanes that add, as masks: every term is one compare's result or fixed for the launch, combined by the scalar unit
+            // a column with a resident bin: added here, not logged (a code Y: to the column's dump cell).  The lanes that add, as
+            // masks: one compare's result and one fixed for the launch, combined by the scalar unit
             const unsigned long long has_acc = __builtin_amdgcn_ballot_w64(acc != 0ull);
             static_for<4>([&](auto cc) {
                 constexpr int c = decltype(cc)::value;
                 if (c == 3 && !resident_wide) return;                            // wave-uniform: no lane has a fourth resident column
-                lds_add_u64_exec<c * (int)(Y * 8u)>(fix_bin + (yf[c] << 3), acc, has_acc & resident_lanes[c] & __builtin_amdgcn_ballot_w64(yf[c] < Y));
+                lds_add_u64_exec<c * (int)(Ys * 8u)>(fix_bin + (yf[c] << 3), acc, has_acc & resident_lanes[c]);
             });
             // what is left to log: fields still below Y once the resident columns' are filled -- whether there is any
             // (none also: a group wholly beyond the edge) is the sign of the record's word
@@ -531,7 +549,7 @@ __global__ void __launch_bounds__(THREADS) k_em_mix(GrpKernelArgs ga) {
 #pragma unroll
                 for (uint32_t rr = 0; rr < 16u; rr++) acc += v[rr];
             }
-            if (owner) n1[j * Y + yy] += acc + (j < n1c ? n1p[j * Y + yy] : 0ull);     // the cell's total, in its bin
+            if (owner) n1[j * Y + yy] += acc + (j < n1c ? n1p[j * Ys + yy] : 0ull);     // the cell's total, in its bin
         }
         BAMM_PHASE(13);
         __syncthreads();
