@@ -227,7 +227,7 @@ CLI = os.path.join(HERE, "BaMMmotif")
 HOST_SHARED = ["io.cpp", "fdr.cpp", "slot_plan.cpp"]
 HOST_SOURCES = HOST_SHARED + ["hooks.cpp"]
 CLI_SOURCES = ["main.cpp", "options.cpp", "context.cpp", "negatives.cpp", "em_run.cpp", "score.cpp", "folds.cpp"] + HOST_SHARED
-HOST_HEADERS = ["bamm_host.h", "slot_plan.h", "options.h", "driver.h"]
+HOST_HEADERS = ["bamm_host.h", "host_util.h", "row_text.h", "neg_sampler.h", "slot_plan.h", "options.h", "driver.h"]
 
 
 def build_host(force: bool = False, verbose: bool = False):

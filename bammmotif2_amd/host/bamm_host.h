@@ -1,7 +1,8 @@
 // C++17 host side of the drop-in `BaMMmotif OUTDIR FASTA [--EM ...]` path: FASTA reader, model
 // file I/O (.hbcp/.hbp/.ihbcp/.ihbp), seeds (MEME PWM / BaMM file / binding sites) and the EM
-// driver over the C ABI (include/bamm_em.h).  Behaviour follows the reference files cited at
-// each function (paths relative to /root/reference/src); the code is written from scratch.
+// driver over the C ABI (include/bamm_em.h), the negative set, the FDR statistics and the output
+// files.  io.cpp holds inputs, models and seeds, fdr.cpp the rest.  Behaviour follows the reference
+// files cited at each function (paths relative to the reference's src/); the code is written from scratch.
 #pragma once
 #include <cstdint>
 #include <functional>
@@ -12,6 +13,7 @@
 
 namespace bammhost {
 
+// ================================================ inputs ================================================
 // ---- sequences (init/SequenceSet.cpp:67-225, init/Alphabet.cpp:10-55, STANDARD alphabet) ----
 // resize() of a vector of bytes with this allocator leaves the new bytes uninitialised: 400 MB of negatives are written
 // by the sampler's threads, a serial zero-fill in front of that costs as much as the sampling (1.0 of 1.6 s)
@@ -34,6 +36,9 @@ struct FastaSet {
 // returns 0, or 1 with `err` holding the reference's message (caller prints + exit(1))
 int read_fasta(const std::string& path, FastaSet& out, std::string& err);
 
+std::string base_name(const std::string& path);   // refinement/utils.h:66-85
+
+// =========================================== models and seeds ===========================================
 // ---- background model (init/BackgroundModel.cpp) ----
 struct BgModel {
     uint32_t K = 2;
@@ -81,7 +86,68 @@ int load_seeds(const std::string& path, const std::string& tag, uint32_t l_flank
                const std::vector<float>& alpha, size_t max_pwm, float glob_q, const BgModel& bg, const uint32_t* yK,
                const uint64_t* off, size_t n_seqs, SeedSet& out, std::string& err, const SeedDevice* dev = nullptr);
 
-std::string base_name(const std::string& path);   // refinement/utils.h:66-85
+// =============================================== negatives ==============================================
+// every core the process may use (affinity mask capped by the cgroup quota): for host work whose result does not
+// depend on how it is cut -- the negative sampler, packing, sorts
+int host_parallelism();
+void set_host_parallelism(int n);           // tests: force a thread count (0 = every granted core again)
+// SeqGenerator::sample_bgseqset_by_fold (seq_generator/SeqGenerator.cpp:188-204) incl. the ctor's
+// srand(42) (:35), calculate_kmer_frequency (:63-110), rescale_kmer_frequency (:112-186, hard-wired
+// to s = 2 like the reference), bgseq_on_rescaled_v (:285-348) and bg_sequence (:222-283).
+// y_s: kmer_ mod 4^(s+1) for every position of the reference sequences (as EM sees them).
+int sample_negatives(const uint32_t* y_s, const uint64_t* off, size_t n_seqs, uint32_t s_order, size_t m_fold,
+                     bool generic, ByteVec& codes_out, std::vector<uint64_t>& off_out, std::string& err, size_t keep_stride = 0);
+
+// ============================================== statistics ==============================================
+struct FdrResult {                      // what FDR::calculatePR / calculatePvalues leave behind (FDR.h:54-84)
+    std::vector<float> zoops_tp, zoops_fp, zoops_fdr, zoops_rec, pn_pvalue, zoops_pvalue;
+    std::vector<float> mops_tp, mops_fp, mops_fdr, mops_rec, mops_pvalue;
+    float occ_frac = 0.f, occ_mult = 0.f;
+};
+// scores may arrive in any order (they are sorted first, FDR.cpp:158-159,203-204)
+void fdr_statistics(std::vector<float> pos_max, std::vector<float> neg_max, std::vector<float> pos_all,
+                    std::vector<float> neg_all, size_t posN, size_t negN, float q, bool mops, bool zoops,
+                    bool with_pvalues, FdrResult& out);
+
+// ScoreSeqSet::calcPvalues (seq_scoring/ScoreSeqSet.cpp:70-126): p-/e-values of every window; the formula itself is
+// csrc/occ_pvalue.h, shared with the device path (bamm_occurrences)
+void mops_pvalues(const float* pos_scores, size_t n_pos_scores, std::vector<float> neg_all, size_t posN,
+                  std::vector<float>& p_out, std::vector<float>& e_out);
+
+// ================================================= files ================================================
+// one float as `ostream << float` prints it at `precision` significant digits (printf %g); `out` holds 48 bytes; returns the length
+size_t format_g(char* out, float x, int precision);
+
+int fdr_write(const std::string& dir, const std::string& basename, const FdrResult& r, size_t posN, size_t negN,
+              bool mops, bool zoops, bool save_prs, bool save_pvalues, std::string& err);   // FDR.cpp:338-410
+
+// the MOPS files of fdr_write from rows fetched range by range [begin, end) -- the device path (bamm_fdr_rows,
+// bamm_fdr_pvalues): the same bytes, host memory for one chunk of rows.  A fetch returns non-zero with `err` set.
+// fdr_write's MOPS half is this writer, fetching from the FdrResult.
+using FdrRowFetch = std::function<int(uint64_t begin, uint64_t end, float* tp, float* fp, float* fdr, float* rec, std::string& err)>;
+using FdrPvalueFetch = std::function<int(uint64_t begin, uint64_t end, float* p, std::string& err)>;
+int fdr_write_mops_chunked(const std::string& dir, const std::string& basename, float occ_mult, uint64_t n_rows, const FdrRowFetch& rows,
+                           uint64_t n_pvalues, const FdrPvalueFetch& pvalues, bool save_prs, bool save_pvalues, std::string& err,
+                           uint64_t chunk = uint64_t(1) << 22);
+
+// --saveLogOdds: FDR::write's .zoops.logOdds / .mops.logOdds (FDR.cpp:416-450) and
+// ScoreSeqSet::writeLogOdds' .logOddsZoops (ScoreSeqSet.cpp:293-331)
+int fdr_logodds_write(const std::string& dir, const std::string& basename, std::vector<float> pos_max, std::vector<float> neg_max,
+                      std::vector<float> pos_all, std::vector<float> neg_all, size_t posN, size_t negN, bool mops, bool zoops,
+                      bool ascending, std::string& err);
+int logodds_zoops_write(const std::string& dir, const std::string& basename, const std::vector<std::string>& headers,
+                        const uint8_t* codes, const uint64_t* off, size_t n_seqs, bool revcomp, bool ss, uint32_t W,
+                        const float* zoops, const uint64_t* z, std::string& err);
+
+// ScoreSeqSet::write (seq_scoring/ScoreSeqSet.cpp:245-291): <basename>.occurrence, one row per window with
+// p < cutoff.  codes/off: FASTA codes of the forward strands; ss as on the command line.
+int occurrence_write(const std::string& dir, const std::string& basename, const std::vector<std::string>& headers,
+                     const uint8_t* codes, const uint64_t* off, size_t n_seqs, bool ss, uint32_t W, const float* p,
+                     const float* e, float cutoff, std::string& err);
+// the same file from the list of windows below the cut-off (bamm_occurrences: ascending sequence, then window start)
+int occurrence_write_hits(const std::string& dir, const std::string& basename, const std::vector<std::string>& headers,
+                          const uint8_t* codes, const uint64_t* off, size_t n_seqs, bool ss, uint32_t W, size_t n_hits,
+                          const uint64_t* seq, const uint32_t* pos, const float* p, const float* e, std::string& err);
 
 // EM::write's <basename>.positions (refinement/EM.cpp:577-601): one row per window whose r reaches the cut-off.
 // codes/off: FASTA codes of the forward strands; ss as on the command line.  r: per sequence L floats (L = the
@@ -93,68 +159,5 @@ int positions_write(const std::string& dir, const std::string& basename, const s
 int positions_write_hits(const std::string& dir, const std::string& basename, const std::vector<std::string>& headers,
                          const uint8_t* codes, const uint64_t* off, size_t n_seqs, bool ss, uint32_t W, size_t n_hits,
                          const uint64_t* seq, const uint32_t* pos, std::string& err);
-
-}  // namespace bammhost
-
-// ======================= evaluation side: negatives, FDR statistics, occurrences ===================
-namespace bammhost {
-
-// SeqGenerator::sample_bgseqset_by_fold (seq_generator/SeqGenerator.cpp:188-204) incl. the ctor's
-// srand(42) (:35), calculate_kmer_frequency (:63-110), rescale_kmer_frequency (:112-186, hard-wired
-// to s = 2 like the reference), bgseq_on_rescaled_v (:285-348) and bg_sequence (:222-283).
-// y_s: kmer_ mod 4^(s+1) for every position of the reference sequences (as EM sees them).
-
-// every core the process may use (affinity mask capped by the cgroup quota): for host work whose result does not
-// depend on how it is cut -- the negative sampler, packing, sorts
-int host_parallelism();
-void set_host_parallelism(int n);           // tests: force a thread count (0 = every granted core again)
-int sample_negatives(const uint32_t* y_s, const uint64_t* off, size_t n_seqs, uint32_t s_order, size_t m_fold,
-                     bool generic, ByteVec& codes_out, std::vector<uint64_t>& off_out, std::string& err, size_t keep_stride = 0);
-
-// one float as `ostream << float` prints it at `precision` significant digits (printf %g); `out` holds 48 bytes; returns the length
-size_t format_g(char* out, float x, int precision);
-
-struct FdrResult {                      // what FDR::calculatePR / calculatePvalues leave behind (FDR.h:54-84)
-    std::vector<float> zoops_tp, zoops_fp, zoops_fdr, zoops_rec, pn_pvalue, zoops_pvalue;
-    std::vector<float> mops_tp, mops_fp, mops_fdr, mops_rec, mops_pvalue;
-    float occ_frac = 0.f, occ_mult = 0.f;
-};
-// scores may arrive in any order (they are sorted first, FDR.cpp:158-159,203-204)
-void fdr_statistics(std::vector<float> pos_max, std::vector<float> neg_max, std::vector<float> pos_all,
-                    std::vector<float> neg_all, size_t posN, size_t negN, float q, bool mops, bool zoops,
-                    bool with_pvalues, FdrResult& out);
-int fdr_write(const std::string& dir, const std::string& basename, const FdrResult& r, size_t posN, size_t negN,
-              bool mops, bool zoops, bool save_prs, bool save_pvalues, std::string& err);   // FDR.cpp:338-410
-
-// the MOPS files of fdr_write from rows fetched range by range [begin, end) -- the device path (bamm_fdr_rows,
-// bamm_fdr_pvalues): the same bytes, host memory for one chunk of rows.  A fetch returns non-zero with `err` set.
-using FdrRowFetch = std::function<int(uint64_t begin, uint64_t end, float* tp, float* fp, float* fdr, float* rec, std::string& err)>;
-using FdrPvalueFetch = std::function<int(uint64_t begin, uint64_t end, float* p, std::string& err)>;
-int fdr_write_mops_chunked(const std::string& dir, const std::string& basename, float occ_mult, uint64_t n_rows, const FdrRowFetch& rows,
-                           uint64_t n_pvalues, const FdrPvalueFetch& pvalues, bool save_prs, bool save_pvalues, std::string& err);
-
-// --saveLogOdds: FDR::write's .zoops.logOdds / .mops.logOdds (FDR.cpp:416-450) and
-// ScoreSeqSet::writeLogOdds' .logOddsZoops (ScoreSeqSet.cpp:293-331)
-int fdr_logodds_write(const std::string& dir, const std::string& basename, std::vector<float> pos_max, std::vector<float> neg_max,
-                      std::vector<float> pos_all, std::vector<float> neg_all, size_t posN, size_t negN, bool mops, bool zoops,
-                      bool ascending, std::string& err);
-int logodds_zoops_write(const std::string& dir, const std::string& basename, const std::vector<std::string>& headers,
-                        const uint8_t* codes, const uint64_t* off, size_t n_seqs, bool revcomp, bool ss, uint32_t W,
-                        const float* zoops, const uint64_t* z, std::string& err);
-
-// ScoreSeqSet::calcPvalues (seq_scoring/ScoreSeqSet.cpp:70-126): p-/e-values of every window; the formula itself is
-// csrc/occ_pvalue.h, shared with the device path (bamm_occurrences)
-void mops_pvalues(const float* pos_scores, size_t n_pos_scores, std::vector<float> neg_all, size_t posN,
-                  std::vector<float>& p_out, std::vector<float>& e_out);
-
-// ScoreSeqSet::write (seq_scoring/ScoreSeqSet.cpp:245-291): <basename>.occurrence, one row per window with
-// p < cutoff.  codes/off: FASTA codes of the forward strands; ss as on the command line.
-int occurrence_write(const std::string& dir, const std::string& basename, const std::vector<std::string>& headers,
-                     const uint8_t* codes, const uint64_t* off, size_t n_seqs, bool ss, uint32_t W, const float* p,
-                     const float* e, float cutoff, std::string& err);
-// the same file from the list of windows below the cut-off (bamm_occurrences: ascending sequence, then window start)
-int occurrence_write_hits(const std::string& dir, const std::string& basename, const std::vector<std::string>& headers,
-                          const uint8_t* codes, const uint64_t* off, size_t n_seqs, bool ss, uint32_t W, size_t n_hits,
-                          const uint64_t* seq, const uint32_t* pos, const float* p, const float* e, std::string& err);
 
 }  // namespace bammhost

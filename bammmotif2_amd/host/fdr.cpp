@@ -1,216 +1,27 @@
-// Evaluation side of the BaMMmotif drop-in: negative-set sampler, FDR / PR statistics and window
-// p-values.  Restated from the reference lines cited in bamm_host.h; fp32 expression order kept.
+// Evaluation and output side of the BaMMmotif drop-in, in bamm_host.h's order: the negative set, the FDR / PR statistics
+// and window p-values, the files.  Restated from the reference lines cited in bamm_host.h; fp32 expression order kept.
 #include <omp.h>
 #include <sched.h>
 
 #include <algorithm>
 #include <atomic>
 #include <charconv>
-#include <cassert>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <fstream>
 #include <functional>
-#include <iomanip>
 #include <thread>
 
 #include "bamm_host.h"
-#include "../csrc/glibc_rand.h"
+#include "neg_sampler.h"
+#include "row_text.h"
 #include "../csrc/occ_pvalue.h"
 #include "../csrc/fdr_rows.h"
 
 namespace bammhost {
 
-static inline size_t ipow4(size_t e) { return size_t(1) << (2 * e); }
-static inline size_t bgoff(size_t k) { return (ipow4(k + 1) - 4) / 3; }
-
-namespace {
-
-struct NegSampler {
-    uint32_t s;
-    std::vector<float> v, range_bar, v_seq;      // flat [k][y]
-    std::vector<size_t> n, n_seq;
-    std::vector<float> A;
-
-    explicit NegSampler(uint32_t s_order) : s(s_order) {
-        const size_t tot = bgoff(s + 1);
-        v.assign(tot, 0.f); range_bar.assign(tot, 0.f); v_seq.assign(tot, 0.f);
-        n.assign(tot, 0); n_seq.assign(tot, 0);
-        A.assign(s + 1, 20.f);                    // SeqGenerator.cpp:29-32
-    }
-
-    void kmer_frequency(const uint32_t* y_s, const uint64_t* off, size_t n_seqs) {   // :63-110
-        std::fill(n.begin(), n.end(), 0);
-        // integer counts: a histogram per host thread, summed -- the same numbers however the sequences are cut
-        const int T = std::max(1, std::min<int>(host_parallelism(), (int)(n_seqs / 4096 + 1)));
-        std::vector<std::vector<size_t>> part((size_t)T, std::vector<size_t>(n.size(), 0));
-#pragma omp parallel for schedule(static) num_threads(T)
-        for (long i = 0; i < (long)n_seqs; i++) {
-            std::vector<size_t>& mine = part[(size_t)omp_get_thread_num()];
-            const size_t L = off[i + 1] - off[i];
-            const uint32_t* km = y_s + off[i];
-            for (uint32_t k = 0; k <= s; k++)
-                for (size_t j = k; j < L; j++) mine[bgoff(k) + km[j] % ipow4(k + 1)]++;
-        }
-        for (auto& pt : part)
-            for (size_t c = 0; c < n.size(); c++) n[c] += pt[c];
-        size_t norm = 0;
-        for (size_t y = 0; y < 4; y++) norm += n[y];
-        float sum = 0.0f;
-        for (size_t y = 0; y < 4; y++) {
-            v[y] = ((float)n[y] + A[0] * 0.25f) / ((float)norm + A[0]);
-            sum += v[y];
-            range_bar[y] = sum;
-        }
-        for (uint32_t k = 1; k <= s; k++) {
-            sum = 0.f;
-            for (size_t y = 0; y < ipow4(k + 1); y++) {
-                const size_t yk = y / 4, y2 = y % ipow4(k);
-                v[bgoff(k) + y] = ((float)n[bgoff(k) + y] + A[k] * v[bgoff(k - 1) + y2]) / ((float)n[bgoff(k - 1) + yk] + A[k]);
-                if (y % 4 == 0) sum = 0.f;
-                sum += v[bgoff(k) + y];
-                range_bar[bgoff(k) + y] = sum;
-            }
-        }
-    }
-
-    void rescale(const uint32_t* km, size_t L) {   // :112-186, written for s = 2
-        std::fill(n_seq.begin(), n_seq.end(), 0);
-        for (uint32_t k = 0; k <= s; k++)
-            for (size_t j = k; j < L; j++) n_seq[bgoff(k) + km[j] % ipow4(k + 1)]++;
-        float sum = 0.f;
-        for (size_t y = 0; y < 4; y++) {
-            v_seq[y] = v[y];
-            sum += v_seq[y];
-            range_bar[y] = sum;
-        }
-        {
-            const uint32_t k = 1;
-            const size_t o1 = bgoff(1), o0 = bgoff(0);
-            for (size_t y = 0; y < 16; y++) {
-                const size_t y2 = y % 4;
-                v_seq[o1 + y] = v[o1 + y] * ((float)n_seq[o1 + y] + A[k - 1] * v[o0 + y2]) / v[o0 + y2] / ((float)L + A[k - 1]);
-            }
-            float norm[4] = {0.f, 0.f, 0.f, 0.f};
-            for (size_t y = 0; y < 16; y++) {
-                const size_t yk = y / 4;
-                v_seq[o1 + y] = ((float)n_seq[o1 + y] + A[k] * v_seq[o1 + y]) / ((float)n_seq[o0 + yk] + A[k]);
-                norm[yk] += v_seq[o1 + y];
-            }
-            for (size_t y = 0; y < 16; y++) v_seq[o1 + y] /= norm[y / 4];
-            for (size_t y = 0; y < 16; y++) {
-                if (y % 4 == 0) sum = 0.0f;
-                sum += v_seq[o1 + y];
-                range_bar[o1 + y] = sum;
-            }
-        }
-        {
-            const uint32_t k = 2;
-            const size_t o2 = bgoff(2), o1 = bgoff(1);
-            for (size_t y = 0; y < 64; y++) {
-                const size_t y2 = y % 16, yk = y / 4;
-                v_seq[o2 + y] = ((float)n_seq[o2 + y] + A[k] * v_seq[o1 + y2]) / ((float)n_seq[o1 + yk] + A[k]);
-                if (y % 4 == 0) sum = 0.0f;
-                sum += v_seq[o2 + y];
-                range_bar[o2 + y] = sum;
-            }
-        }
-    }
-
-    // glibc's rand() restated (csrc/glibc_rand.h): used only after its first draws have been checked against
-    // srand(42)/rand() of the running libc, otherwise the sampler stays on rand(); jump(n) lets every host thread
-    // start in the middle of the one stream.  Every later rand() consumer reseeds (FDR.cpp:153).
-    bamm::GlibcRandStream stream;
-
-
-    // F sequences of the same length from the same tables, drawn one after the other from the
-    // stream (sequence f consumes draws [f*L, (f+1)*L)) but advanced position by position together:
-    // the per-base dependency chain (context -> bars -> base -> context) of one sequence overlaps
-    // with those of the others.
-    // keep (nullable): keep[f] == 0 -> sequence f still consumes its L draws of the stream but is not generated; the
-    // kept ones are written one after the other (FDR.cpp:58-60 only ever scores every cvFold-th negative)
-    void draw_many(size_t L, size_t F, uint8_t* seqs, std::vector<float>& rnd, std::vector<size_t>& ctx, const uint8_t* keep = nullptr) {
-        if (s >= L || F == 1) {
-            for (size_t f = 0; f < F; f++) {
-                if (keep && !keep[f]) { for (size_t k = 0; k < L; k++) (void)stream.next(); continue; }
-                draw(L, seqs);
-                seqs += L;
-            }
-            return;
-        }
-        rnd.resize(F * L);
-        for (size_t k = 0; k < F * L; k++) rnd[k] = (float)stream.next() / (float)RAND_MAX;
-        ctx.assign(F, 0);
-        std::vector<uint8_t*>& dst = dst_scratch;
-        dst.assign(F, nullptr);
-        {
-            uint8_t* at = seqs;
-            for (size_t f = 0; f < F; f++) if (!keep || keep[f]) { dst[f] = at; at += L; }
-        }
-        for (size_t f = 0; f < F; f++) {               // the first s bases: lower-order bars (as in draw())
-            if (!dst[f]) continue;
-            uint8_t* seq = dst[f];
-            const float* r = rnd.data() + f * L;
-            for (uint8_t y = 0; y < 4; y++)
-                if (r[0] <= range_bar[y]) { seq[0] = y + 1; break; }
-            for (size_t i = 1; i < s; i++) {
-                size_t yk = 0;
-                for (size_t k = i; k > 0; k--) yk += (size_t)(seq[i - k] - 1) * ipow4(k);
-                for (size_t y = yk, a = 1; y < yk + 4; y++, a++) {
-                    seq[i] = (uint8_t)a;
-                    if (r[i] <= range_bar[bgoff(i) + y]) break;
-                }
-            }
-            for (size_t k = s; k > 0; k--) ctx[f] = ctx[f] * 4 + (size_t)(seq[s - k] - 1);
-        }
-        const size_t ctx_mask = ipow4(s) - 1;
-        const float* bar = range_bar.data() + bgoff(s);
-        for (size_t i = s; i < L; i++)
-            for (size_t f = 0; f < F; f++) {
-                if (!dst[f]) continue;
-                const float* b4 = bar + ctx[f] * 4;
-                const float random = rnd[f * L + i];
-                const uint8_t a = (uint8_t)(1 + (random > b4[0]) + (random > b4[1]) + (random > b4[2]));
-                dst[f][i] = a;
-                ctx[f] = (ctx[f] * 4 + (size_t)(a - 1)) & ctx_mask;
-            }
-    }
-    std::vector<uint8_t*> dst_scratch;
-
-    void draw(size_t L, uint8_t* seq) {             // :222-283 == :296-341 (same sampling loop)
-        float random = (float)stream.next() / (float)RAND_MAX;
-        for (uint8_t y = 0; y < 4; y++)
-            if (random <= range_bar[y]) { seq[0] = y + 1; break; }
-        for (size_t i = 1; i < s && i < L; i++) {
-            size_t yk = 0;
-            for (size_t k = i; k > 0; k--) yk += (size_t)(seq[i - k] - 1) * ipow4(k);
-            random = (float)stream.next() / (float)RAND_MAX;
-            for (size_t y = yk, a = 1; y < yk + 4; y++, a++) {
-                seq[i] = (uint8_t)a;
-                if (random <= range_bar[bgoff(i) + y]) break;
-            }
-        }
-        if (s >= L) return;
-        // context of the previous s bases, rolled forward (yk = sum_k (seq[i-k]-1) * 4^k)
-        const size_t ctx_mod = ipow4(s);
-        size_t ctx = 0;
-        for (size_t k = s; k > 0; k--) ctx = ctx * 4 + (size_t)(seq[s - k] - 1);
-        const float* bar = range_bar.data() + bgoff(s);
-        for (size_t i = s; i < L; i++) {
-            const float* b4 = bar + ctx * 4;
-            random = (float)stream.next() / (float)RAND_MAX;
-            // first base whose cumulative bar reaches `random`, the last one when none does; the
-            // bars are running sums (non-decreasing), so counting the bars below is the same thing
-            const uint8_t a = (uint8_t)(1 + (random > b4[0]) + (random > b4[1]) + (random > b4[2]));
-            seq[i] = a;
-            ctx = (ctx * 4 + (size_t)(a - 1)) & (ctx_mod - 1);
-        }
-    }
-};
-
-}  // namespace
-
+// ---------------------------------------------------------------------------------- negatives ----
 // Host threads for work whose result does not depend on how it is cut (this sampler, packing, sorts): every core
 // the process may use -- the affinity mask capped by the cgroup CPU quota -- whatever --threads says (the
 // reference's flag sized its OpenMP EM loops, Global.cpp:331-333; a container may show 256 CPUs and grant 16).
@@ -297,6 +108,7 @@ int sample_negatives(const uint32_t* y_s, const uint64_t* off, size_t n_seqs, ui
     return 0;
 }
 
+// --------------------------------------------------------------------------------- statistics ----
 // Scores in the reference's order (std::sort with greater / less, FDR.cpp:158-159,203-204,288-289) on every granted core:
 // sorted runs per thread, merged pairwise.  A sorted sequence of floats is the same whatever produced it (equal
 // scores are indistinguishable -- the rare +0 / -0 pair aside, which no statistic tells apart).
@@ -432,6 +244,25 @@ void fdr_statistics(std::vector<float> posMax, std::vector<float> negMax, std::v
     }
 }
 
+void mops_pvalues(const float* pos_scores, size_t n_pos_scores, std::vector<float> neg, size_t posN,
+                  std::vector<float>& p_out, std::vector<float>& e_out) {
+    const size_t negN = neg.size();                    // ScoreSeqSet.cpp:75-93
+    std::sort(neg.begin(), neg.end(), std::less<float>());
+    const bamm::OccScalars sc = bamm::occ_scalars(neg.data(), negN);
+    p_out.resize(n_pos_scores);
+    e_out.resize(n_pos_scores);
+    for (size_t i = 0; i < n_pos_scores; i++) {        // ScoreSeqSet.cpp:97-125: the branches are occ_window_pvalue's
+        const float Sl = pos_scores[i];
+        const size_t FPl = neg.end() - std::upper_bound(neg.begin(), neg.end(), Sl);
+        float SlHigher = 0.f, SlLower = 0.f;
+        if (bamm::occ_uses_neighbours(FPl, sc)) { SlHigher = neg[negN - FPl - 1]; SlLower = neg[negN - FPl]; }
+        const float p = bamm::occ_window_pvalue(Sl, FPl, SlHigher, SlLower, sc);
+        p_out[i] = p;
+        e_out[i] = p * (float)posN;
+    }
+}
+
+// -------------------------------------------------------------------------------------- files ----
 // `ostream << float` at precision P, i.e. printf's %.Pg, without the general-purpose machinery: the P significant digits
 // come from one double multiplication (a float times a power of ten up to 1e22 is one rounding away from exact) and
 // are used only when that rounding cannot have changed them -- the scaled value further than 1e-6 from a half; anything
@@ -488,96 +319,21 @@ size_t format_g(char* out, float xf, int P) {
     return (size_t)(o - out);
 }
 
-namespace {
-
-// rows of floats exactly as `ostream << float` prints them (printf %g at the stream's precision),
-// collected in memory and written once: the reference ends every row with std::endl, i.e. one
-// write() per line, which at 2.2 M rows costs more than computing the statistics
-struct alignas(128) RowWriter {                          // a line of its own: the string's length changes with every number, and the threads' writers sit side by side
-    std::string buf;
-    int precision;
-    explicit RowWriter(int prec = 6) : precision(prec) { buf.reserve(1 << 20); }
-    void num(float x) {
-        char tmp[48];
-        buf.append(tmp, format_g(tmp, x, precision));
-    }
-    void tab() { buf.push_back('\t'); }
-    void nl() { buf.push_back('\n'); }
-    void flush_to(std::ofstream& f) { f.write(buf.data(), (std::streamsize)buf.size()); buf.clear(); }
-    void maybe_flush(std::ofstream& f) { if (buf.size() > (1 << 20) - 256) flush_to(f); }
-};
-
-// rows [0, n) formatted by row(w, i) on every granted core -- rounds of one chunk per thread, the chunks written in
-// order: the same bytes as one writer walking all rows (formatting 11 M numbers is most of what the files cost), and
-// the threads' buffers are reused from round to round (fresh pages are slow to come by in a container)
-template <class Row>
-void write_rows(std::ofstream& f, size_t n, int precision, Row&& row) {
-    constexpr size_t kChunk = 16384;
-    const int T = (int)std::max<size_t>(1, std::min<size_t>((size_t)host_parallelism(), n / kChunk + 1));
-    std::vector<RowWriter> part((size_t)T, RowWriter(precision));
-    for (size_t base = 0; base < n; base += kChunk * (size_t)T) {
-#pragma omp parallel for schedule(static, 1) num_threads(T)
-        for (int t = 0; t < T; t++) {
-            RowWriter& w = part[(size_t)t];
-            const size_t a = std::min(n, base + kChunk * (size_t)t), b = std::min(n, a + kChunk);
-            for (size_t i = a; i < b; i++) row(w, i);
-        }
-        for (auto& w : part) w.flush_to(f);
-    }
-}
-
-}  // namespace
-
-int fdr_write(const std::string& dir, const std::string& basename, const FdrResult& r, size_t posN, size_t negN,
-              bool mops, bool zoops, bool save_prs, bool save_pvalues, std::string& err) {
-    const std::string opath = dir + '/' + basename;
-    if (save_prs) {
-        if (zoops) {                                   // FDR.cpp:385-407
-            std::ofstream f(opath + ".zoops.stats");
-            if (!f.is_open()) { err = "Error: Cannot write into output directory: " + dir; return 1; }
-            f << "TP" << '\t' << "FP" << '\t' << "FDR" << '\t' << "Recall" << '\t' << "p-value" << '\t'
-              << (float)negN / (float)posN << '\t' << r.occ_frac << std::endl;
-            write_rows(f, r.zoops_fdr.size(), 6, [&](RowWriter& w, size_t i) {
-                w.num(r.zoops_tp[i]); w.tab(); w.num(r.zoops_fp[i]); w.tab(); w.num(r.zoops_fdr[i]); w.tab();
-                w.num(r.zoops_rec[i]); w.tab(); w.num(r.pn_pvalue[i]); w.tab(); w.nl();
-            });
-        }
-        if (mops) {                                    // FDR.cpp:409-425
-            std::ofstream f(opath + ".mops.stats");
-            f << "TP" << '\t' << "FP" << '\t' << "FDR" << '\t' << "Recall" << '\t' << r.occ_mult << std::endl;
-            write_rows(f, r.mops_fdr.size(), 6, [&](RowWriter& w, size_t i) {
-                w.num(r.mops_tp[i]); w.tab(); w.num(r.mops_fp[i]); w.tab(); w.num(r.mops_fdr[i]); w.tab();
-                w.num(r.mops_rec[i]); w.tab(); w.nl();
-            });
-        }
-    }
-    if (save_pvalues) {                                // FDR.cpp:428-449, setprecision(3)
-        if (zoops) {
-            std::ofstream f(opath + ".zoops.pvalues");
-            write_rows(f, r.zoops_pvalue.size(), 3, [&](RowWriter& w, size_t i) { w.num(r.zoops_pvalue[i]); w.nl(); });
-        }
-        if (mops) {
-            std::ofstream f(opath + ".mops.pvalues");
-            write_rows(f, r.mops_pvalue.size(), 3, [&](RowWriter& w, size_t i) { w.num(r.mops_pvalue[i]); w.nl(); });
-        }
-    }
-    return 0;
-}
-
-// .mops.stats / .mops.pvalues of fdr_write from rows that are fetched range by range (bamm_fdr_rows / bamm_fdr_pvalues):
-// the same bytes, with a few million rows on the host at a time instead of every window's
+// .mops.stats / .mops.pvalues (FDR.cpp:409-425, :428-449 at setprecision(3)) from rows that are fetched range by range
+// (the device path: bamm_fdr_rows / bamm_fdr_pvalues): `chunk` rows on the host at a time instead of every window's
 int fdr_write_mops_chunked(const std::string& dir, const std::string& basename, float occ_mult, uint64_t n_rows, const FdrRowFetch& rows,
-                           uint64_t n_pvalues, const FdrPvalueFetch& pvalues, bool save_prs, bool save_pvalues, std::string& err) {
-    constexpr uint64_t kChunk = uint64_t(1) << 22;
+                           uint64_t n_pvalues, const FdrPvalueFetch& pvalues, bool save_prs, bool save_pvalues, std::string& err,
+                           uint64_t chunk) {
+    if (chunk == 0) { err = "Error: the MOPS files cannot be written zero rows at a time"; return 1; }
     const std::string opath = dir + '/' + basename;
     std::vector<float> col[4];
     if (save_prs) {
-        std::ofstream f(opath + ".mops.stats");
-        if (!f.is_open()) { err = "Error: Cannot write into output directory: " + dir; return 1; }
+        std::ofstream f;
+        if (!open_output(f, opath + ".mops.stats", dir, err)) return 1;
         f << "TP" << '\t' << "FP" << '\t' << "FDR" << '\t' << "Recall" << '\t' << occ_mult << std::endl;
-        for (auto& c : col) c.resize((size_t)std::min(kChunk, n_rows));
-        for (uint64_t at = 0; at < n_rows; at += kChunk) {
-            const uint64_t stop = std::min(n_rows, at + kChunk);
+        for (auto& c : col) c.resize((size_t)std::min(chunk, n_rows));
+        for (uint64_t at = 0; at < n_rows; at += chunk) {
+            const uint64_t stop = std::min(n_rows, at + chunk);
             if (rows(at, stop, col[0].data(), col[1].data(), col[2].data(), col[3].data(), err)) return 1;
             write_rows(f, (size_t)(stop - at), 6, [&](RowWriter& w, size_t i) {
                 w.num(col[0][i]); w.tab(); w.num(col[1][i]); w.tab(); w.num(col[2][i]); w.tab(); w.num(col[3][i]); w.tab(); w.nl();
@@ -585,16 +341,45 @@ int fdr_write_mops_chunked(const std::string& dir, const std::string& basename, 
         }
     }
     if (save_pvalues) {
-        std::ofstream f(opath + ".mops.pvalues");
-        if (!f.is_open()) { err = "Error: Cannot write into output directory: " + dir; return 1; }
-        col[0].resize((size_t)std::min(kChunk, n_pvalues));
-        for (uint64_t at = 0; at < n_pvalues; at += kChunk) {
-            const uint64_t stop = std::min(n_pvalues, at + kChunk);
+        std::ofstream f;
+        if (!open_output(f, opath + ".mops.pvalues", dir, err)) return 1;
+        col[0].resize((size_t)std::min(chunk, n_pvalues));
+        for (uint64_t at = 0; at < n_pvalues; at += chunk) {
+            const uint64_t stop = std::min(n_pvalues, at + chunk);
             if (pvalues(at, stop, col[0].data(), err)) return 1;
             write_rows(f, (size_t)(stop - at), 3, [&](RowWriter& w, size_t i) { w.num(col[0][i]); w.nl(); });
         }
     }
     return 0;
+}
+
+int fdr_write(const std::string& dir, const std::string& basename, const FdrResult& r, size_t posN, size_t negN,
+              bool mops, bool zoops, bool save_prs, bool save_pvalues, std::string& err) {
+    const std::string opath = dir + '/' + basename;
+    if (zoops && save_prs) {                           // FDR.cpp:385-407
+        std::ofstream f;
+        if (!open_output(f, opath + ".zoops.stats", dir, err)) return 1;
+        f << "TP" << '\t' << "FP" << '\t' << "FDR" << '\t' << "Recall" << '\t' << "p-value" << '\t'
+          << (float)negN / (float)posN << '\t' << r.occ_frac << std::endl;
+        write_rows(f, r.zoops_fdr.size(), 6, [&](RowWriter& w, size_t i) {
+            w.num(r.zoops_tp[i]); w.tab(); w.num(r.zoops_fp[i]); w.tab(); w.num(r.zoops_fdr[i]); w.tab();
+            w.num(r.zoops_rec[i]); w.tab(); w.num(r.pn_pvalue[i]); w.tab(); w.nl();
+        });
+    }
+    if (zoops && save_pvalues) {                       // FDR.cpp:428-449, setprecision(3)
+        std::ofstream f;
+        if (!open_output(f, opath + ".zoops.pvalues", dir, err)) return 1;
+        write_rows(f, r.zoops_pvalue.size(), 3, [&](RowWriter& w, size_t i) { w.num(r.zoops_pvalue[i]); w.nl(); });
+    }
+    if (!mops) return 0;
+    auto range = [](const std::vector<float>& v, uint64_t begin, uint64_t end, float* dst) { std::copy(v.begin() + (ptrdiff_t)begin, v.begin() + (ptrdiff_t)end, dst); };
+    return fdr_write_mops_chunked(dir, basename, r.occ_mult, r.mops_fdr.size(),
+        [&](uint64_t a, uint64_t b, float* tp, float* fp, float* fdr, float* rec, std::string&) {
+            range(r.mops_tp, a, b, tp); range(r.mops_fp, a, b, fp); range(r.mops_fdr, a, b, fdr); range(r.mops_rec, a, b, rec);
+            return 0;
+        },
+        r.mops_pvalue.size(), [&](uint64_t a, uint64_t b, float* p, std::string&) { range(r.mops_pvalue, a, b, p); return 0; },
+        save_prs, save_pvalues, err);
 }
 
 // FDR::write, saveLogOdds_ branch (FDR.cpp:416-450): score i of the positives beside score
@@ -605,15 +390,13 @@ int fdr_write_mops_chunked(const std::string& dir, const std::string& basename, 
 int fdr_logodds_write(const std::string& dir, const std::string& basename, std::vector<float> posMax, std::vector<float> negMax,
                       std::vector<float> posAll, std::vector<float> negAll, size_t posN, size_t negN, bool mops, bool zoops,
                       bool ascending, std::string& err) {
-    auto order = [&](std::vector<float>& v) {
-        sort_scores(v, !ascending);
-    };
     auto emit = [&](const std::string& path, std::vector<float>& pos, std::vector<float>& neg) {
-        order(pos); order(neg);
-        std::ofstream f(path);
-        if (!f.is_open()) { err = "Error: Cannot write into output directory: " + dir; return 1; }
-        f << "positive" << '\t' << "negative" << std::endl;
+        sort_scores(pos, !ascending);
+        sort_scores(neg, !ascending);
+        std::ofstream f;
+        if (!open_output(f, path, dir, err)) return 1;
         RowWriter w(6);
+        w.text("positive\tnegative\n");
         for (size_t i = 0; i < pos.size(); i++) {
             const size_t j = i * negN / posN;
             if (j >= neg.size()) break;
@@ -634,104 +417,66 @@ int fdr_logodds_write(const std::string& dir, const std::string& basename, std::
 int logodds_zoops_write(const std::string& dir, const std::string& basename, const std::vector<std::string>& headers,
                         const uint8_t* codes, const uint64_t* off, size_t n_seqs, bool revcomp, bool ss, uint32_t W,
                         const float* zoops, const uint64_t* z, std::string& err) {
-    std::ofstream f(dir + '/' + basename + ".logOddsZoops");
-    if (!f.is_open()) { err = "Error: Cannot write into output directory: " + dir; return 1; }
-    f << "seq\tlength\tstrand\tstart..end\tpattern\tzoops_score" << std::endl;
-    static const char B[] = "NACGT";
-    for (size_t n = 0; n < n_seqs; n++) {
-        const size_t L0 = off[n + 1] - off[n], L = revcomp ? 2 * L0 + 1 : L0;
-        size_t seqlen = L;
-        if (!ss) seqlen = (seqlen - 1) / 2;
-        const uint8_t* c = codes + off[n];
-        f << headers[n] << '\t' << seqlen << '\t' << ((z[n] < seqlen) ? '+' : '-') << '\t' << z[n] + 1 << ".." << z[n] + W << '\t';
-        for (size_t m = z[n]; m < z[n] + W; m++) {
-            char b = 'N';                                      // Sequence::getSequence(): forward, N, reverse complement
-            if (m < L0) b = B[c[m] <= 4 ? c[m] : 0];
-            else if (revcomp && m > L0 && m < L) { const uint8_t x = c[2 * L0 - m]; b = (x >= 1 && x <= 4) ? B[5 - x] : 'N'; }
-            f << b;
-        }
-        f << '\t' << std::setprecision(3) << zoops[n] << std::endl;
-    }
-    return 0;
+    WindowRows out{headers, codes, off, W, revcomp, !ss};
+    if (!out.open(dir, basename + ".logOddsZoops", "\tzoops_score", err)) return 1;
+    for (size_t n = 0; n < n_seqs; n++) out.row(n, z[n], {zoops[n]});
+    return out.close();
 }
 
-void mops_pvalues(const float* pos_scores, size_t n_pos_scores, std::vector<float> neg, size_t posN,
-                  std::vector<float>& p_out, std::vector<float>& e_out) {
-    const size_t negN = neg.size();                    // ScoreSeqSet.cpp:75-93
-    std::sort(neg.begin(), neg.end(), std::less<float>());
-    const bamm::OccScalars sc = bamm::occ_scalars(neg.data(), negN);
-    p_out.resize(n_pos_scores);
-    e_out.resize(n_pos_scores);
-    for (size_t i = 0; i < n_pos_scores; i++) {        // ScoreSeqSet.cpp:97-125: the branches are occ_window_pvalue's
-        const float Sl = pos_scores[i];
-        const size_t FPl = neg.end() - std::upper_bound(neg.begin(), neg.end(), Sl);
-        float SlHigher = 0.f, SlLower = 0.f;
-        if (bamm::occ_uses_neighbours(FPl, sc)) { SlHigher = neg[negN - FPl - 1]; SlLower = neg[negN - FPl]; }
-        const float p = bamm::occ_window_pvalue(Sl, FPl, SlHigher, SlLower, sc);
-        p_out[i] = p;
-        e_out[i] = p * (float)posN;
-    }
-}
-
-namespace {
-
-// one row of ScoreSeqSet::write (ScoreSeqSet.cpp:262-288) for window i of sequence n
-struct OccurrenceRows {
-    std::ofstream f;
-    const std::vector<std::string>& headers;
-    const uint8_t* codes;
-    const uint64_t* off;
-    bool ss;
-    uint32_t W;
-    void row(size_t n, size_t i, float p, float e) {
-        static const char B[] = "NACGT";
-        const size_t L0 = off[n + 1] - off[n], L = ss ? L0 : 2 * L0 + 1, seqlen = ss ? L : (L - 1) / 2;
-        const uint8_t* c = codes + off[n];
-        auto base_at = [&](size_t b) -> char {             // Sequence::getSequence(): forward, N, reverse complement
-            if (b < L0) return B[c[b] <= 4 ? c[b] : 0];
-            if (ss || b == L0) return 'N';
-            const uint8_t x = c[2 * L0 - b];
-            return (x >= 1 && x <= 4) ? B[5 - x] : 'N';
-        };
-        f << headers[n] << '\t' << seqlen << '\t' << ((i < seqlen) ? '+' : '-') << '\t' << i + 1 << ".." << i + W << '\t';
-        for (size_t m = i; m < i + W; m++) f << base_at(m);
-        f << '\t' << std::setprecision(3) << p << '\t' << e << std::endl;
-    }
-    bool open(const std::string& dir, const std::string& basename, std::string& err) {
-        f.open(dir + '/' + basename + ".occurrence");
-        if (!f.is_open()) { err = "Error: Cannot write into output directory: " + dir; return false; }
-        f << "seq\tlength\tstrand\tstart..end\tpattern\tp-value\te-value" << std::endl;
-        return true;
-    }
-};
-
-}  // namespace
-
+// ScoreSeqSet::write's .occurrence (ScoreSeqSet.cpp:245-291): one row per window with p < cutoff, p- and e-value behind it
 int occurrence_write(const std::string& dir, const std::string& basename, const std::vector<std::string>& headers,
                      const uint8_t* codes, const uint64_t* off, size_t n_seqs, bool ss, uint32_t W, const float* p,
                      const float* e, float cutoff, std::string& err) {
-    OccurrenceRows rows{{}, headers, codes, off, ss, W};
-    if (!rows.open(dir, basename, err)) return 1;
+    WindowRows out{headers, codes, off, W, !ss, !ss};
+    if (!out.open(dir, basename + ".occurrence", "\tp-value\te-value", err)) return 1;
     size_t o = 0;
     for (size_t n = 0; n < n_seqs; n++) {
-        const size_t L0 = off[n + 1] - off[n], L = ss ? L0 : 2 * L0 + 1, LW1 = L - W + 1;
+        const size_t LW1 = out.full_length(n) - W + 1;
         for (size_t i = 0; i < LW1; i++)
-            if (p[o + i] < cutoff) rows.row(n, i, p[o + i], e[o + i]);
+            if (p[o + i] < cutoff) out.row(n, i, {p[o + i], e[o + i]});
         o += LW1;
     }
-    return 0;
+    return out.close();
 }
 
 int occurrence_write_hits(const std::string& dir, const std::string& basename, const std::vector<std::string>& headers,
                           const uint8_t* codes, const uint64_t* off, size_t n_seqs, bool ss, uint32_t W, size_t n_hits,
                           const uint64_t* seq, const uint32_t* pos, const float* p, const float* e, std::string& err) {
-    OccurrenceRows rows{{}, headers, codes, off, ss, W};
-    if (!rows.open(dir, basename, err)) return 1;
+    WindowRows out{headers, codes, off, W, !ss, !ss};
+    if (!out.open(dir, basename + ".occurrence", "\tp-value\te-value", err)) return 1;
     for (size_t h = 0; h < n_hits; h++) {
         if (seq[h] >= n_seqs) { err = "Error: occurrence list names a sequence beyond the set"; return 1; }
-        rows.row((size_t)seq[h], pos[h], p[h], e[h]);
+        out.row((size_t)seq[h], pos[h], {p[h], e[h]});
     }
-    return 0;
+    return out.close();
+}
+
+// EM::write's .positions (refinement/EM.cpp:577-601): one row per window whose r reaches the cut-off, the window alone
+int positions_write(const std::string& dir, const std::string& basename, const std::vector<std::string>& headers,
+                    const uint8_t* codes, const uint64_t* off, size_t n_seqs, bool ss, uint32_t W, const float* r, float cutoff,
+                    std::string& err) {
+    WindowRows out{headers, codes, off, W, !ss, !ss};
+    if (!out.open(dir, basename + ".positions", "", err)) return 1;
+    size_t ro = 0;
+    for (size_t n = 0; n < n_seqs; n++) {
+        const size_t L = out.full_length(n);
+        for (size_t i = 0; i + W <= L; i++)
+            if (r[ro + L - W - i] >= cutoff) out.row(n, i);
+        ro += L;
+    }
+    return out.close();
+}
+
+int positions_write_hits(const std::string& dir, const std::string& basename, const std::vector<std::string>& headers,
+                         const uint8_t* codes, const uint64_t* off, size_t n_seqs, bool ss, uint32_t W, size_t n_hits,
+                         const uint64_t* seq, const uint32_t* pos, std::string& err) {
+    WindowRows out{headers, codes, off, W, !ss, !ss};
+    if (!out.open(dir, basename + ".positions", "", err)) return 1;
+    for (size_t h = 0; h < n_hits; h++) {
+        if (seq[h] >= n_seqs || (size_t)pos[h] + W > out.full_length((size_t)seq[h])) { err = "Error: site list names a window beyond the set"; return 1; }
+        out.row((size_t)seq[h], pos[h]);
+    }
+    return out.close();
 }
 
 }  // namespace bammhost

@@ -1,17 +1,33 @@
 // extern "C" test hooks over the C++ host code (libbamm_host.so), so that the CPU test-suite can
 // drive the FASTA reader, the seeders and the model-file writers through ctypes.
+#include <algorithm>
 #include <cstring>
 
 #include <omp.h>
 
 #include <charconv>
 #include "bamm_host.h"
+#include "host_util.h"
 #include "slot_plan.h"
 #include "../csrc/occ_pvalue.h"
 
 using namespace bammhost;
 
 static thread_local std::string g_err;
+
+static BgModel bg_from(uint32_t order, const float* vbg) {
+    BgModel bg;
+    bg.K = order;
+    bg.v.assign(vbg, vbg + bamm_bg_size(order));
+    return bg;
+}
+
+// "<prefix>0", "<prefix>1", ... or, not numbered, the prefix n times
+static std::vector<std::string> numbered_headers(const std::string& prefix, uint64_t n, bool numbered = true) {
+    std::vector<std::string> headers;
+    for (uint64_t i = 0; i < n; i++) headers.push_back(numbered ? prefix + std::to_string(i) : prefix);
+    return headers;
+}
 
 extern "C" {
 
@@ -32,10 +48,8 @@ int bh_read_fasta(const char* path, uint64_t* n_seqs, uint64_t* n_codes, uint8_t
 }
 
 int bh_write_bg(const char* dir, const char* base, uint32_t K, const float* alpha, const float* v) {
-    BgModel bg;
-    bg.K = K;
+    BgModel bg = bg_from(K, v);
     bg.alpha.assign(alpha, alpha + K + 1);
-    bg.v.assign(v, v + bamm_bg_size(K));
     return bg_write(dir, base, bg, g_err);
 }
 
@@ -51,13 +65,9 @@ int bh_read_bg(const char* path, uint32_t* K, float* alpha, float* v, uint32_t c
 
 int bh_write_motif(const char* dir, const char* base, uint32_t W, uint32_t K, const float* v, uint32_t bg_order, const float* vbg) {
     Motif m;
-    std::vector<float> alpha(K + 1, 1.f);
-    motif_alloc(m, W, K, alpha, 0.3f);
+    motif_alloc(m, W, K, std::vector<float>(K + 1, 1.f), 0.3f);
     m.v.assign(v, v + bamm_v_size(K, W));
-    BgModel bg;
-    bg.K = bg_order;
-    bg.v.assign(vbg, vbg + bamm_bg_size(bg_order));
-    motif_calculate_p(m, bg);
+    motif_calculate_p(m, bg_from(bg_order, vbg));
     return motif_write(dir, base, m, g_err);
 }
 
@@ -66,16 +76,12 @@ static int load_seed_impl(const char* path, const char* tag, uint32_t l_flank, u
                  uint64_t max_pwm, float glob_q, uint32_t bg_order, const float* vbg, const bamm_packed* packed,
                  uint32_t index, uint32_t* n_motifs, uint32_t* w_out, float* q_out, float* v_out, uint64_t v_cap,
                  const SeedDevice* dev) {
-    BgModel bg;
-    bg.K = bg_order;
-    bg.v.assign(vbg, vbg + bamm_bg_size(bg_order));
     std::vector<uint32_t> yK(packed->total_len ? packed->total_len : 1);
     if (bamm_unpack_y(packed, K, yK.data())) { g_err = bamm_last_error(); return 1; }
-    std::vector<uint64_t> off(packed->n_seqs + 1, 0);
-    for (uint64_t n = 0; n < packed->n_seqs; n++) off[n + 1] = off[n] + packed->len[n];
     SeedSet seeds;
     std::vector<float> al(alpha, alpha + K + 1);
-    if (load_seeds(path, tag, l_flank, r_flank, K, al, max_pwm, glob_q, bg, yK.data(), off.data(), packed->n_seqs, seeds, g_err, dev)) return 1;
+    if (load_seeds(path, tag, l_flank, r_flank, K, al, max_pwm, glob_q, bg_from(bg_order, vbg), yK.data(), offsets_of(packed).data(), packed->n_seqs, seeds,
+                   g_err, dev)) return 1;
     *n_motifs = (uint32_t)seeds.motifs.size();
     if (index >= seeds.motifs.size()) { g_err = "motif index out of range"; return 1; }
     const Motif& m = seeds.motifs[index];
@@ -90,18 +96,12 @@ static int load_seed_impl(const char* path, const char* tag, uint32_t l_flank, u
 // the host path (std::mt19937 + std::discrete_distribution) or, with ctx/seqs, the device path
 int bh_pwm_sites(const float* pwm, uint32_t W, uint32_t K, const float* alpha, uint32_t bg_order, const float* vbg,
                  const bamm_packed* packed, float q, float* v_out, uint32_t* z_out, bamm_ctx* ctx, bamm_seqs* seqs) {
-    BgModel bg;
-    bg.K = bg_order;
-    bg.v.assign(vbg, vbg + bamm_bg_size(bg_order));
     Motif m;
     motif_alloc(m, W, K, std::vector<float>(alpha, alpha + K + 1), q);
-    std::vector<uint64_t> off(packed->n_seqs + 1, 0);
-    for (uint64_t n = 0; n < packed->n_seqs; n++) off[n + 1] = off[n] + packed->len[n];
     std::vector<uint32_t> yK(packed->total_len ? packed->total_len : 1), z;
     if (bamm_unpack_y(packed, K, yK.data())) { g_err = bamm_last_error(); return 1; }
-    SeedDevice dev;
-    dev.ctx = ctx; dev.seqs = seqs;
-    if (motif_init_from_pwm(m, std::vector<float>(pwm, pwm + 4 * (size_t)W), bg, yK.data(), off.data(), packed->n_seqs, q,
+    const SeedDevice dev{ctx, seqs};
+    if (motif_init_from_pwm(m, std::vector<float>(pwm, pwm + 4 * (size_t)W), bg_from(bg_order, vbg), yK.data(), offsets_of(packed).data(), packed->n_seqs, q,
                             ctx ? &dev : nullptr, g_err, &z)) return 1;
     memcpy(v_out, m.v.data(), m.v.size() * sizeof(float));
     memcpy(z_out, z.data(), z.size() * sizeof(uint32_t));
@@ -120,8 +120,7 @@ int bh_load_seed_dev(const char* path, const char* tag, uint32_t l_flank, uint32
                      uint64_t max_pwm, float glob_q, uint32_t bg_order, const float* vbg, const bamm_packed* packed,
                      uint32_t index, uint32_t* n_motifs, uint32_t* w_out, float* q_out, float* v_out, uint64_t v_cap,
                      bamm_ctx* ctx, bamm_seqs* seqs) {
-    SeedDevice dev;
-    dev.ctx = ctx; dev.seqs = seqs;
+    const SeedDevice dev{ctx, seqs};
     return load_seed_impl(path, tag, l_flank, r_flank, K, alpha, max_pwm, glob_q, bg_order, vbg, packed, index, n_motifs,
                           w_out, q_out, v_out, v_cap, &dev);
 }
@@ -146,9 +145,7 @@ int bh_occ_window_pvalues(const float* score, const uint64_t* fp, const float* h
 
 int bh_occurrence_hits(const char* dir, const char* base, const uint8_t* codes, const uint64_t* off, uint64_t n_seqs, int ss,
                        uint32_t W, uint64_t n_hits, const uint64_t* seq, const uint32_t* pos, const float* p, const float* e) {
-    std::vector<std::string> headers;
-    for (uint64_t n = 0; n < n_seqs; n++) headers.push_back("seq" + std::to_string(n));
-    return occurrence_write_hits(dir, base, headers, codes, off, n_seqs, ss != 0, W, n_hits, seq, pos, p, e, g_err);
+    return occurrence_write_hits(dir, base, numbered_headers("seq", n_seqs), codes, off, n_seqs, ss != 0, W, n_hits, seq, pos, p, e, g_err);
 }
 
 // EM::write's .positions from a site list / from dense r; headers: n_seqs C strings
@@ -164,18 +161,9 @@ int bh_positions(const char* dir, const char* base, const char* const* headers, 
     return positions_write(dir, base, hd, codes, off, n_seqs, ss != 0, W, r, cutoff, g_err);
 }
 
-}  // extern "C"
-
 // ---- evaluation-side hooks ---------------------------------------------------------------
-extern "C" {
 
 // negatives for a packed (positive) set; two-call protocol (codes == NULL -> sizes only)
-int bh_sample_negatives_strided(const bamm_packed* packed, uint32_t s_order, uint64_t m_fold, int generic, uint64_t keep_stride,
-                                uint64_t* n_out, uint64_t* n_codes, uint8_t* codes, uint64_t* off);
-int bh_sample_negatives(const bamm_packed* packed, uint32_t s_order, uint64_t m_fold, int generic, uint64_t* n_out,
-                        uint64_t* n_codes, uint8_t* codes, uint64_t* off) {
-    return bh_sample_negatives_strided(packed, s_order, m_fold, generic, 0, n_out, n_codes, codes, off);
-}
 // keep_stride > 1: only every keep_stride-th negative (what --FDR scores, FDR.cpp:58-60) is generated and returned
 int bh_sample_negatives_strided(const bamm_packed* packed, uint32_t s_order, uint64_t m_fold, int generic, uint64_t keep_stride,
                                 uint64_t* n_out, uint64_t* n_codes, uint8_t* codes, uint64_t* off) {
@@ -184,9 +172,7 @@ int bh_sample_negatives_strided(const bamm_packed* packed, uint32_t s_order, uin
     if (!codes) {
         std::vector<uint32_t> ys(packed->total_len ? packed->total_len : 1);
         if (bamm_unpack_y(packed, s_order, ys.data())) { g_err = bamm_last_error(); return 1; }
-        std::vector<uint64_t> poff(packed->n_seqs + 1, 0);
-        for (uint64_t n = 0; n < packed->n_seqs; n++) poff[n + 1] = poff[n] + packed->len[n];
-        if (sample_negatives(ys.data(), poff.data(), packed->n_seqs, s_order, m_fold, generic != 0, c, o, g_err, (size_t)keep_stride)) return 1;
+        if (sample_negatives(ys.data(), offsets_of(packed).data(), packed->n_seqs, s_order, m_fold, generic != 0, c, o, g_err, (size_t)keep_stride)) return 1;
         *n_out = o.size() - 1;
         *n_codes = c.size();
         return 0;
@@ -194,6 +180,10 @@ int bh_sample_negatives_strided(const bamm_packed* packed, uint32_t s_order, uin
     memcpy(codes, c.data(), c.size());
     memcpy(off, o.data(), o.size() * sizeof(uint64_t));
     return 0;
+}
+int bh_sample_negatives(const bamm_packed* packed, uint32_t s_order, uint64_t m_fold, int generic, uint64_t* n_out,
+                        uint64_t* n_codes, uint8_t* codes, uint64_t* off) {
+    return bh_sample_negatives_strided(packed, s_order, m_fold, generic, 0, n_out, n_codes, codes, off);
 }
 
 int bh_fdr_stats(const float* pos_max, uint64_t n_pos_max, const float* neg_max, uint64_t n_neg_max, const float* pos_all,
@@ -220,6 +210,17 @@ int bh_fdr_mops_rows(const float* pos_all, uint64_t n_pos, const float* neg_all,
     return 0;
 }
 
+// .mops.stats / .mops.pvalues from caller-provided rows, handed to the writer `chunk` rows at a time through its fetchers
+int bh_fdr_mops_chunked(const float* tp, const float* fp, const float* fdr, const float* rec, uint64_t n_rows, const float* p, uint64_t n_p,
+                        float occ_mult, uint64_t chunk, const char* dir, const char* base) {
+    return fdr_write_mops_chunked(dir, base, occ_mult, n_rows,
+        [&](uint64_t a, uint64_t b, float* t, float* f, float* d, float* r, std::string&) {
+            std::copy(tp + a, tp + b, t); std::copy(fp + a, fp + b, f); std::copy(fdr + a, fdr + b, d); std::copy(rec + a, rec + b, r);
+            return 0;
+        },
+        n_p, [&](uint64_t a, uint64_t b, float* out, std::string&) { std::copy(p + a, p + b, out); return 0; }, true, true, g_err, chunk);
+}
+
 // tests: format_g against std::to_chars (which is printf's %g) on n floats; returns the number of differing strings and
 // the first offender's bits
 uint64_t bh_format_g_check(const float* x, uint64_t n, int precision, uint32_t* first_bad_bits) {
@@ -244,9 +245,7 @@ int bh_fdr_logodds(const float* pos_max, uint64_t n_pos_max, const float* neg_ma
 
 int bh_logodds_zoops(const char* dir, const char* base, const char* header_prefix, int number_headers, const uint8_t* codes,
                      const uint64_t* off, uint64_t n_seqs, int revcomp, int ss, uint32_t W, const float* zoops, const uint64_t* z) {
-    std::vector<std::string> headers;
-    for (uint64_t n = 0; n < n_seqs; n++) headers.push_back(number_headers ? header_prefix + std::to_string(n) : std::string(header_prefix));
-    return logodds_zoops_write(dir, base, headers, codes, off, n_seqs, revcomp != 0, ss != 0, W, zoops, z, g_err);
+    return logodds_zoops_write(dir, base, numbered_headers(header_prefix, n_seqs, number_headers != 0), codes, off, n_seqs, revcomp != 0, ss != 0, W, zoops, z, g_err);
 }
 
 int bh_mops_pvalues(const float* pos_scores, uint64_t n_pos, const float* neg_all, uint64_t n_neg, uint64_t posN, float* p_out,
@@ -260,9 +259,7 @@ int bh_mops_pvalues(const float* pos_scores, uint64_t n_pos, const float* neg_al
 
 int bh_occurrence(const char* dir, const char* base, const uint8_t* codes, const uint64_t* off, uint64_t n_seqs, int ss,
                   uint32_t W, const float* p, const float* e, float cutoff) {
-    std::vector<std::string> headers;
-    for (uint64_t n = 0; n < n_seqs; n++) headers.push_back("seq" + std::to_string(n));
-    return occurrence_write(dir, base, headers, codes, off, n_seqs, ss != 0, W, p, e, cutoff, g_err);
+    return occurrence_write(dir, base, numbered_headers("seq", n_seqs), codes, off, n_seqs, ss != 0, W, p, e, cutoff, g_err);
 }
 
 // the CLI's GPU slot plan (slot_plan.h) as arrays: devices, em_slots, in_em_group and runs_folds hold n_slots entries (the

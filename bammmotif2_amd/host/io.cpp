@@ -1,4 +1,4 @@
-// FASTA reader and model-file I/O of the BaMMmotif drop-in path.  See bamm_host.h.
+// Inputs, models and seeds of the BaMMmotif drop-in path: FASTA reader, model-file I/O, seeders.  See bamm_host.h.
 #include <omp.h>
 #include <sys/stat.h>
 
@@ -13,16 +13,12 @@
 
 #include <fcntl.h>
 #include <sys/mman.h>
-#include <sys/stat.h>
 #include <unistd.h>
 
 #include "bamm_host.h"
+#include "host_util.h"
 
 namespace bammhost {
-
-static inline size_t ipow4(size_t e) { return size_t(1) << (2 * e); }
-static inline size_t voff(size_t k, size_t W) { return W * ((ipow4(k + 1) - 4) / 3); }
-static inline size_t bgoff(size_t k) { return (ipow4(k + 1) - 4) / 3; }
 
 std::string base_name(const std::string& path) {
     // text between the last '/' and the last '.' (refinement/utils.h:66-85)
@@ -239,8 +235,8 @@ int bg_read(const std::string& path, BgModel& out, std::string& err) {
 int bg_write(const std::string& dir, const std::string& basename, const BgModel& bg, std::string& err) {
     const uint32_t K = bg.K;
     {   // conditional probabilities (BackgroundModel.cpp:359-377)
-        std::ofstream file(dir + '/' + basename + ".hbcp");
-        if (!file.is_open()) { err = "Error: Cannot write into output directory: " + dir; return 1; }
+        std::ofstream file;
+        if (!open_output(file, dir + '/' + basename + ".hbcp", dir, err)) return 1;
         file << "# K = " << K << std::endl;
         file << "# A =";
         for (uint32_t k = 0; k <= K; k++) file << " " << bg.alpha[k];
@@ -256,8 +252,8 @@ int bg_write(const std::string& dir, const std::string& basename, const BgModel&
     for (size_t y = 0; y < 4; y++) p[y] = bg.v[y];
     for (uint32_t k = 1; k <= K; k++)
         for (size_t y = 0; y < ipow4(k + 1); y++) p[bgoff(k) + y] = bg.v[bgoff(k) + y] * p[bgoff(k - 1) + y / 4];
-    std::ofstream file(dir + '/' + basename + ".hbp");
-    if (!file.is_open()) { err = "Error: Cannot write into output directory: " + dir; return 1; }
+    std::ofstream file;
+    if (!open_output(file, dir + '/' + basename + ".hbp", dir, err)) return 1;
     file << "# K = " << K << std::endl;
     file << "# A =";
     for (uint32_t k = 0; k <= K; k++) file << std::fixed << std::setprecision(2) << " " << bg.alpha[k];
@@ -443,8 +439,8 @@ int motif_init_from_sites(Motif& m, const std::string& path, uint32_t l_flank, u
 }
 
 int motif_write(const std::string& dir, const std::string& basename, const Motif& m, std::string& err) {
-    std::ofstream fv(dir + '/' + basename + ".ihbcp"), fp(dir + '/' + basename + ".ihbp");
-    if (!fv.is_open() || !fp.is_open()) { err = "Error: Cannot write into output directory: " + dir; return 1; }
+    std::ofstream fv, fp;
+    if (!open_output(fv, dir + '/' + basename + ".ihbcp", dir, err) || !open_output(fp, dir + '/' + basename + ".ihbp", dir, err)) return 1;
     for (uint32_t j = 0; j < m.W; j++) {                      // Motif.cpp:531-546
         for (uint32_t k = 0; k <= m.K; k++) {
             for (size_t y = 0; y < ipow4(k + 1); y++) {
@@ -540,67 +536,6 @@ int load_seeds(const std::string& path, const std::string& tag, uint32_t l_flank
     }
     err = "Error: unknown initial model tag " + tag;
     return 1;
-}
-
-// ---- EM::write's .positions (refinement/EM.cpp:577-601) ----
-namespace {
-
-// one row per window: header, the length shown (one strand's), strand, start..end (1-based), the window's bases
-struct PositionRows {
-    std::ofstream f;
-    const std::vector<std::string>& headers;
-    const uint8_t* codes;
-    const uint64_t* off;
-    bool ss;
-    uint32_t W;
-    bool open(const std::string& dir, const std::string& basename, std::string& err) {
-        f.open(dir + '/' + basename + ".positions");
-        if (!f.is_open()) { err = "Error: Cannot write into output directory: " + dir; return false; }
-        f << "seq\tlength\tstrand\tstart..end\tpattern\n";
-        return true;
-    }
-    size_t full_length(size_t n) const { const size_t L0 = off[n + 1] - off[n]; return ss ? L0 : 2 * L0 + 1; }
-    void row(size_t n, size_t i) {
-        static const char B[] = "NACGT";
-        const size_t L0 = off[n + 1] - off[n], shown = ss ? L0 : (full_length(n) - 1) / 2;
-        const uint8_t* c = codes + off[n];
-        f << headers[n] << '\t' << shown << '\t' << ((i < shown) ? '+' : '-') << '\t' << i + 1 << ".." << i + W << '\t';
-        for (size_t b = i; b < i + W; b++) {                 // Sequence::getSequence(): forward, N, reverse complement
-            if (b < L0) f << B[c[b] <= 4 ? c[b] : 0];
-            else if (ss || b == L0) f << 'N';
-            else { const uint8_t x = c[2 * L0 - b]; f << ((x >= 1 && x <= 4) ? B[5 - x] : 'N'); }
-        }
-        f << '\n';
-    }
-};
-
-}  // namespace
-
-int positions_write(const std::string& dir, const std::string& basename, const std::vector<std::string>& headers,
-                    const uint8_t* codes, const uint64_t* off, size_t n_seqs, bool ss, uint32_t W, const float* r, float cutoff,
-                    std::string& err) {
-    PositionRows rows{{}, headers, codes, off, ss, W};
-    if (!rows.open(dir, basename, err)) return 1;
-    size_t ro = 0;
-    for (size_t n = 0; n < n_seqs; n++) {
-        const size_t L = rows.full_length(n);
-        for (size_t i = 0; i + W <= L; i++)
-            if (r[ro + L - W - i] >= cutoff) rows.row(n, i);
-        ro += L;
-    }
-    return 0;
-}
-
-int positions_write_hits(const std::string& dir, const std::string& basename, const std::vector<std::string>& headers,
-                         const uint8_t* codes, const uint64_t* off, size_t n_seqs, bool ss, uint32_t W, size_t n_hits,
-                         const uint64_t* seq, const uint32_t* pos, std::string& err) {
-    PositionRows rows{{}, headers, codes, off, ss, W};
-    if (!rows.open(dir, basename, err)) return 1;
-    for (size_t h = 0; h < n_hits; h++) {
-        if (seq[h] >= n_seqs || (size_t)pos[h] + W > rows.full_length((size_t)seq[h])) { err = "Error: site list names a window beyond the set"; return 1; }
-        rows.row((size_t)seq[h], pos[h]);
-    }
-    return 0;
 }
 
 }  // namespace bammhost

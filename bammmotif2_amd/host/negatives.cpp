@@ -1,5 +1,6 @@
 // The negative set of --scoreSeqset / --FDR: sampler, packing and upload on a thread of their own (see NegativeSet in driver.h).
 #include "driver.h"
+#include "host_util.h"
 
 namespace bammhost {
 
@@ -29,16 +30,14 @@ void NegativeSet::body(const Run& run, const bamm_packed* use, bamm_packed* filt
         if (rc == BAMM_OK) {
             on_device = true;
             if (filtered) bamm_packed_free(filtered);
-            off.assign(1, 0);
-            for (uint64_t n = 0; n < npk->n_seqs; n++) off.push_back(off.back() + npk->len[n]);
+            off = offsets_of(npk);
         }
     }
     if (!npk) {
         std::vector<uint32_t, DefaultInitAlloc<uint32_t>> ys(use->total_len ? use->total_len : 1);   // every cell is written
-        std::vector<uint64_t> uoff(n_pos + 1, 0);
+        const std::vector<uint64_t> uoff = offsets_of(use);
         std::string serr;
         const int rc = bamm_unpack_y(use, (uint32_t)o.sOrder, ys.data());
-        for (uint64_t n = 0; n < n_pos; n++) uoff[n + 1] = uoff[n] + use->len[n];
         if (filtered) bamm_packed_free(filtered);            // the thread is the last reader of the kept positives' packing
         if (rc) return fail_abi("unpack");
         if (sample_negatives(ys.data(), uoff.data(), n_pos, (uint32_t)o.sOrder, mFold, o.genericNeg, codes, off, serr, stride)) { err = serr; return; }

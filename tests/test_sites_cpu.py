@@ -1,5 +1,5 @@
 """EM sites on the device, the parts that need no GPU: the C ABI declares and binds bamm_em_sites and its accessors, and
-the .positions writer that takes a site list (host/io.cpp, what `--saveBaMMs` feeds from the device) reproduces a numpy
+the .positions writer that takes a site list (host/fdr.cpp, what `--saveBaMMs` feeds from the device) reproduces a numpy
 restatement of EM::write's loop (refinement/EM.cpp:585-601) on the responsibilities of the reference's own third pass
 (tests/golden: r_2) -- as does the writer that walks dense r (`--hostPositions`)."""
 import ctypes as C
