@@ -52,16 +52,21 @@ def test_negative_sampler_does_not_depend_on_threads(generic, host):
     c = Case(name="neg_thr", N=700, L0=60, W=8, K=2, ragged=25)
     packed = bm.PackedSeqs.from_codes(c.codes, c.in_off, False, seed=42)
     out = []
-    for threads in (1, 5):
-        host.bh_set_threads(threads)
-        n, m = C.c_uint64(), C.c_uint64()
-        assert host.bh_sample_negatives(packed._p, 2, C.c_uint64(3), generic, C.byref(n), C.byref(m), None, None) == 0
-        codes = np.zeros(m.value, np.uint8)
-        off = np.zeros(n.value + 1, np.uint64)
-        assert host.bh_sample_negatives(packed._p, 2, C.c_uint64(3), generic, C.byref(n), C.byref(m),
-                                        codes.ctypes.data_as(C.c_void_p), off.ctypes.data_as(C.c_void_p)) == 0
-        out.append((codes, off))
-    host.bh_auto_threads()
+    gomp = C.CDLL("libgomp.so.1")                              # bh_set_threads also sets the process's OpenMP thread count,
+    before = gomp.omp_get_max_threads()                        # on which the sums of later tests' fp32 oracle depend: left as found
+    try:
+        for threads in (1, 5):
+            host.bh_set_threads(threads)
+            n, m = C.c_uint64(), C.c_uint64()
+            assert host.bh_sample_negatives(packed._p, 2, C.c_uint64(3), generic, C.byref(n), C.byref(m), None, None) == 0
+            codes = np.zeros(m.value, np.uint8)
+            off = np.zeros(n.value + 1, np.uint64)
+            assert host.bh_sample_negatives(packed._p, 2, C.c_uint64(3), generic, C.byref(n), C.byref(m),
+                                            codes.ctypes.data_as(C.c_void_p), off.ctypes.data_as(C.c_void_p)) == 0
+            out.append((codes, off))
+    finally:
+        host.bh_auto_threads()
+        gomp.omp_set_num_threads(before)
     assert out[0][0].size > 0 and out[0][0].min() >= 1 and out[0][0].max() <= 4
     assert np.array_equal(out[0][1], out[1][1]) and np.array_equal(out[0][0], out[1][0])
     # --FDR only ever scores every cvFold-th negative (FDR.cpp:58-60): asked for just those, the sampler returns

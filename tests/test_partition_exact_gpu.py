@@ -29,12 +29,13 @@ SHAPES = [
 ]
 
 
-def accumulator(ctx, hip, pk, begin, end, shape, vbg, A, v0, launch=(0, 0)):
+def accumulator(ctx, hip, pk, begin, end, shape, vbg, A, v0, launch=(0, 0), bound=None):
+    """bound: bamm_em_params.n_seqs_bound, which sizes the accumulator's unit (default: the whole set's size)."""
     ctx.set_launch(*launch)
     ctx.set_tuning(**shape["tune"])
     try:
         ss = bm.SeqSet(ctx, pk, begin, end)
-        em = bm.EM(ctx, ss, shape["K"], shape["W"], vbg, A, v0, 0.3, n_seqs_bound=shape["N"])
+        em = bm.EM(ctx, ss, shape["K"], shape["W"], vbg, A, v0, 0.3, n_seqs_bound=shape["N"] if bound is None else bound)
     finally:
         ctx.set_launch(0, 0)
         ctx.set_tuning(group_layout=-1)
