@@ -15,9 +15,9 @@ import subprocess
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libbamm_em.so")
-SOURCES = ["model.hip", "kernels.hip", "grouped.hip", "grouped_long.hip", "grouped_xl.hip", "grouped_mix.hip", "grouped_mix1.hip", "lane_records.hip", "mask.hip", "seed.hip", "long_seq.hip", "scorer.hip", "prep.hip", "negs.hip", "occ.hip", "sites.hip", "fdr.hip", "ctx.cpp", "seqs.cpp", "plan.cpp", "em_pass.cpp", "em.cpp",
+SOURCES = ["model.hip", "kernels.hip", "grouped.hip", "grouped_long.hip", "grouped_xl.hip", "grouped_mix.hip", "grouped_mix1.hip", "lane_records.hip", "mask.hip", "seed.hip", "long_seq.hip", "scorer.hip", "em_tiles.hip", "prep.hip", "negs.hip", "occ.hip", "sites.hip", "fdr.hip", "ctx.cpp", "seqs.cpp", "plan.cpp", "em_pass.cpp", "em.cpp",
            "score.cpp", "occurrences.cpp", "sites.cpp", "fdr_stats.cpp", "comm.cpp", "pack.cpp"]
-HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "device_utils.h"), os.path.join(CSRC, "mclass.h"), os.path.join(CSRC, "grouped_kernel.h"), os.path.join(CSRC, "mixed_kernel.h"), os.path.join(CSRC, "lane_records.h"), os.path.join(CSRC, "update_kernel.h"), os.path.join(CSRC, "phase_clock.h"),
+HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "device_utils.h"), os.path.join(CSRC, "mclass.h"), os.path.join(CSRC, "tiles.h"), os.path.join(CSRC, "grouped_kernel.h"), os.path.join(CSRC, "mixed_kernel.h"), os.path.join(CSRC, "lane_records.h"), os.path.join(CSRC, "update_kernel.h"), os.path.join(CSRC, "phase_clock.h"),
            os.path.join(HERE, "..", "include", "bamm_em.h")]
 # -Rpass-analysis=kernel-resource-usage: registers / scratch / spills of every kernel go to the compiler's
 # stderr, which is kept per translation unit (build/<tu>.remarks) and checked by check_resources().
@@ -33,7 +33,7 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=o
 # occ.hip restates a host fp32 expression bit for bit: IEEE division and kept fp32 denormals named explicitly (the compiler's defaults today)
 # ... and so does fdr.hip (csrc/fdr_rows.h, shared with host/fdr.cpp)
 _IEEE = ["-fhip-fp32-correctly-rounded-divide-sqrt", "-fno-gpu-flush-denormals-to-zero"]
-TU_FLAGS = {"occ.hip": _IEEE, "fdr.hip": _IEEE, "grouped_long.hip": ["-falign-functions=16384"], "grouped_xl.hip": ["-falign-functions=16384"], "kernels.hip": ["-falign-functions=16384"], "scorer.hip": ["-falign-functions=16384"]}
+TU_FLAGS = {"occ.hip": _IEEE, "fdr.hip": _IEEE, "grouped_long.hip": ["-falign-functions=16384"], "grouped_xl.hip": ["-falign-functions=16384"], "kernels.hip": ["-falign-functions=16384"], "scorer.hip": ["-falign-functions=16384"], "em_tiles.hip": ["-falign-functions=16384"]}
 OBJDIR = os.path.join(HERE, "build")
 RESOURCES = os.path.join(OBJDIR, "resources.json")
 

@@ -312,6 +312,21 @@ uint32_t score_tile_threads();
 // k_score_tile over every tile, then the per-sequence maxima into k.zoops / k.z
 int launch_score_tiles(const ScoreTileArgs& a, uint32_t blocks, hipStream_t st);
 
+// ---- long sequences through the EM pass, tile by tile (em_tiles.hip) ----
+struct EmTileArgs {
+    EmKernelArgs e;              // sv: the long sequences of one bucket; a sequence outside sv.mask is skipped inside the kernels
+    const uint32_t* tile_off;    // [sv.count + 1] prefix sums of the sequences' tile counts (every sequence, no mask)
+    uint32_t n_tiles, stride;    // tile_off[sv.count]; windows a tile owns (em_tile_geometry)
+    double*  tile_z;             // [n_tiles] a tile's share of its sequence's sum over windows (EM.cpp:180)
+    float*   rec_invz;           // [sv.count] 1 / Z of the sequence in bucket slot t
+};
+// the one tile geometry for motifs of width W; false when W leaves no stride of at least 16
+bool em_tile_geometry(uint32_t W, uint32_t* tile_positions, uint32_t* stride);
+uint32_t em_tile_threads();
+// One pass over the tiles: every tile's share of Z, every sequence's 1 / Z (and, with e.acc, its three statistics), then --
+// when the pass accumulates or writes r -- the responsibilities and the counts.  blocks == kPrimeOnly: loads the code object.
+int launch_em_tiles(const EmTileArgs& a, bool accum, bool write_r, uint32_t blocks, hipStream_t st);
+
 
 // ---- window p-values on the device (occ.hip; ScoreSeqSet.cpp:70-126) ----
 struct OccCand {                 // a positive window the host has to look at

@@ -1,5 +1,5 @@
-// Device-side helpers shared by the sequence kernels (kernels.hip, grouped.hip, scorer.hip): DPP wave shifts,
-// the 2^-40 fixed-point conversion, hand-issued LDS gathers / predicated LDS adds, the 2-bit
+// Device-side helpers shared by the sequence kernels (kernels.hip, grouped.hip, scorer.hip, em_tiles.hip): DPP wave shifts,
+// the 2^-40 fixed-point conversion, hand-issued LDS gathers / predicated LDS adds, the dense M-step walk, the 2-bit
 // sequence decode and the cold paths' (seed.hip, mask.hip, long_seq.hip) position-by-position decode.
 // Everything is `__device__ __forceinline__` in an anonymous namespace.
 #pragma once
@@ -169,6 +169,40 @@ __device__ __forceinline__ void lds_add_slot(uint32_t byte_addr, unsigned long l
         typedef __attribute__((address_space(3))) unsigned long long lds_u64;
         if (pad_ok && v != 0ull) atomicAdd((unsigned long long*)(lds_u64*)(size_t)byte_addr, v);
 #endif
+    }
+}
+
+// ---- dense M-step walk over `ncols` columns, last column first ---------------------------------
+// F is kept as a ring: after t shifts logical slot m lives in F[(m+t) mod M]; the shift itself is one
+// in-place DPP pair on F[t] (the value leaving becomes the value arriving from the next lane), so no
+// register moves.  The ring index must be a compile-time value, i.e. the walk is unrolled: up to 32
+// positions per lane over a whole turn (M steps, M*M adds); beyond that a turn would be thousands of
+// adds, the compiler gives up on the unrolling and the arrays land in scratch memory (5x slower).
+// Those classes unroll 8 steps and then turn the ring back by 8 places (2*M register moves per 8*M adds).
+template <int M>
+__device__ __forceinline__ void dense_count_walk(uint32_t ncols, uint32_t col, uint32_t stride, const uint32_t (&ya)[M],
+                                                 unsigned long long (&F)[M], unsigned long long (&nz)[M],
+                                                 const unsigned long long (&padm)[M], const uint32_t (&y)[M], uint32_t Y) {
+    constexpr int TB = M <= 32 ? M : 8;
+    for (uint32_t jb = 0; jb < ncols; jb += TB) {
+#pragma unroll
+        for (int t = 0; t < TB; t++) {
+            if (jb + t < ncols) {
+#pragma unroll
+                for (int m = 0; m < M; m++)
+                    lds_add_slot<M>(col + ya[m], F[(m + t) % M], padm[m], nz[(m + t) % M], y[m] != Y);
+                F[t] = wave_shl1_u64(F[t]);
+                nz[t] = __ballot(F[t] != 0ull);
+                col -= stride;
+            }
+        }
+        if constexpr (TB < M) {
+            unsigned long long Fr[M], nr[M];
+#pragma unroll
+            for (int m = 0; m < M; m++) { Fr[m] = F[(m + TB) % M]; nr[m] = nz[(m + TB) % M]; }
+#pragma unroll
+            for (int m = 0; m < M; m++) { F[m] = Fr[m]; nz[m] = nr[m]; }
+        }
     }
 }
 

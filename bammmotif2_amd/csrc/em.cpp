@@ -44,7 +44,7 @@ int bamm::dense_r_on_device(bamm_em* em, uint64_t begin, uint64_t end, DevBlocks
         a.acc = nullptr;                                    // responsibilities only
         a.r_out = d_r; a.r_base = base; a.seq_begin = (uint32_t)begin; a.seq_end = (uint32_t)end;
         a.fix_scale = 1.0f;
-        if (bk.mclass == kLongClass) { rc = launch_long_em(a, false, true, false, bk.blocks, st); continue; }
+        if (bk.mclass == kLongClass) { rc = launch_long_bucket(em->ctx, bk, a, false, true, false, false, st); continue; }
         rc = launch_fused(em, bk, false, true, a, bucket_threads(em->ctx, bk), st);
     }
     *out = DenseR{d_r, base, false};
@@ -608,6 +608,27 @@ int bamm_em_plan_paths(bamm_em* em, int* sliced, int* e_fused, uint64_t* long_se
     if (sliced) *sliced = em->sliced ? 1 : 0;
     if (e_fused) *e_fused = em->sliced && em->e_fused ? 1 : 0;
     if (long_seqs) *long_seqs = l;
+    return BAMM_OK;
+}
+
+int bamm_em_tile_geometry(uint32_t W, uint32_t* tile_positions, uint32_t* stride) {
+    if (!em_tile_geometry(W, tile_positions, stride)) {
+        set_error("bamm_em_tile_geometry: W=%u leaves a tile no stride of at least 16 positions", W);
+        return BAMM_ERR_ARG;
+    }
+    return BAMM_OK;
+}
+
+int bamm_em_tile_plan(bamm_em* em, uint64_t* tiled_seqs, uint64_t* tiles, uint64_t* window_seqs) {
+    if (!em) { set_error("null em"); return BAMM_ERR_ARG; }
+    uint64_t ts = 0, nt = 0, ws = 0;
+    for (auto& b : em->ebuckets) {
+        if (b.mclass != kLongClass) continue;
+        if (b.tiled) { ts += b.count; nt += b.n_tiles; } else ws += b.count;
+    }
+    if (tiled_seqs) *tiled_seqs = ts;
+    if (tiles) *tiles = nt;
+    if (window_seqs) *window_seqs = ws;
     return BAMM_OK;
 }
 

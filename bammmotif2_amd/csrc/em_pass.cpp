@@ -106,6 +106,19 @@ int launch_fused(bamm_em* em, const EmBucket& eb, bool accum, bool write_r, EmKe
     return launch_em_grp(eb.mclass, accum, write_r, ga, eb.blocks, threads, st);
 }
 
+int launch_long_bucket(const bamm_ctx* c, const EmBucket& bk, const EmKernelArgs& a, bool accum, bool write_r, bool slot_layout,
+                       bool prime_only, hipStream_t st) {
+    if (!bk.tiled) return launch_long_em(a, accum, write_r, slot_layout, prime_only ? kPrimeOnly : bk.blocks, st);
+    EmTileArgs ta{};
+    ta.e = a;
+    ta.tile_off = bk.d_tile_off; ta.n_tiles = bk.n_tiles; ta.stride = bk.tile_stride;
+    ta.tile_z = bk.d_tile_z; ta.rec_invz = bk.d_rec_invz;
+    // a block per CU (its count table takes most of the CU's LDS), a wave per tile; nothing in the result depends on it
+    const uint32_t waves = em_tile_threads() / 64u;
+    const uint32_t blocks = std::min(c->blocks ? c->blocks : (uint32_t)std::max(1, c->num_cus), (bk.n_tiles + waves - 1u) / waves);
+    return launch_em_tiles(ta, accum, write_r, prime_only ? kPrimeOnly : blocks, st);
+}
+
 // clear whatever a pass left unconsumed (accumulate without update, getR replay, a fused sequence cut short)
 int clean_accumulator(bamm_em* em) {
     if (!em->acc_dirty) return BAMM_OK;
@@ -208,7 +221,7 @@ int run_accumulate(bamm_em* em, bool accum, bool replay_last, bool dense_r, int 
             const bool want_r = em->sliced && dense_r;
             if (want_r && !em->d_state && (rc = em->mem.scratch(&em->d_state, (size_t)s->total_len))) return rc;
             a.r_out = em->d_state;
-            if ((rc = launch_long_em(a, accum, want_r, want_r && !em->e_fused, bk.blocks, st))) return rc;
+            if ((rc = launch_long_bucket(em->ctx, bk, a, accum, want_r, want_r && !em->e_fused, false, st))) return rc;
             continue;
         }
         const uint32_t threads = bucket_threads(em->ctx, bk);

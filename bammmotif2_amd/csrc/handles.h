@@ -71,6 +71,13 @@ struct EmBucket {                // one kernel launch of an EM pass
     const uint2* d_lane_rec = nullptr;   // mixed rows: the bucket's lane records (lane_records.h), owned by the handle
     uint32_t blocks = 0, logc = 0, sparse_cap = 0, sparse_bytes = 0;
     double work = 0;
+    // a long bucket (mclass == kLongClass) that goes tile by tile (em_tiles.hip) instead of window by window (long_seq.hip):
+    // built once per handle, without the fold mask (getR needs every sequence's tiles), in the handle's own DevBlocks
+    bool tiled = false;
+    uint32_t n_tiles = 0, tile_stride = 0;
+    const uint32_t* d_tile_off = nullptr;   // [count + 1] prefix sums of the sequences' tile counts
+    double* d_tile_z = nullptr;             // [n_tiles] written and read within one pass
+    float* d_rec_invz = nullptr;            // [count] likewise
 };
 
 // The host-side state one model update moves -- the part of bamm_em (which derives from it) that optimize() copies after
@@ -102,6 +109,7 @@ struct bamm_ctx {
     uint32_t blocks = 0, threads = 0;   // 0 = default
     // bamm_ctx_set_tuning: kernel-selection switches for benchmarks and the cross-kernel parity tests
     bool use_grouped = true, use_sparse = true, use_e_fused = true, use_e_list = true, use_fused_update = true, use_adaptive_lists = true, use_update_blocks = true;
+    bool use_em_tiles = true;           // EM handles take sequences beyond the length classes tile by tile (em_tiles.hip); read at bamm_em_create
     bool use_score_tiles = true;        // the scorer takes sequences beyond the length classes tile by tile (scorer.hip); read at every scoring call
     uint32_t list_threshold_pct = 45;   // sliced path: a pass takes lists when fewer than this share of the windows was non-zero in the pass before
     uint32_t group_size = 0;            // 0 = planner's choice
@@ -413,6 +421,10 @@ int launch_fused(bamm_em* em, const EmBucket& eb, bool accum, bool write_r, EmKe
                  hipStream_t st, const UpdateArgs* fuse = nullptr);
 int clean_accumulator(bamm_em* em);
 int run_accumulate(bamm_em* em, bool accum, bool replay_last = false, bool dense_r = false, int fuse_q_window = -1);
+// The one way a bucket of mclass kLongClass is launched -- by a pass, by getR / bamm_em_sites, and to load its code object
+// (prime_only: nothing is launched) alike: tile by tile when the plan says so (EmBucket::tiled), else window by window.
+int launch_long_bucket(const bamm_ctx* c, const EmBucket& bk, const EmKernelArgs& a, bool accum, bool write_r, bool slot_layout,
+                       bool prime_only, hipStream_t st);
 int allreduce_words(bamm_em* em, void* dev_ptr, size_t n_words);
 int run_allreduce(bamm_em* em);
 float* q_write_slot(bamm_em* em);

@@ -20,7 +20,7 @@ int prime_bucket(bamm_ctx* c, const bamm_em_params& prm, uint32_t Y, bool sliced
     if (hipSetDevice(c->device) != hipSuccess) { set_error("hipSetDevice failed"); return BAMM_ERR_HIP; }
     EmKernelArgs a{};
     a.K = prm.K; a.W = prm.W; a.Y = Y;
-    if (eb.mclass == kLongClass) return launch_long_em(a, true, false, false, kPrimeOnly, c->stream);
+    if (eb.mclass == kLongClass) return launch_long_bucket(c, eb, a, true, false, false, true, c->stream);
     const uint32_t threads = bucket_threads(c, eb);
     if (sliced || !eb.grouped) {                             // k_em_seq, the slices and the list walk share kernels.hip
         a.logC = 0;
@@ -132,6 +132,25 @@ int plan_launches(bamm_em* em, bool global_tables, const uint8_t* seq_mask, Prim
             EmBucket eb;
             eb.mclass = kLongClass; eb.count = b.count; eb.d_idx = b.d_idx;
             eb.work = b.mclass == kLongClass ? b.work : (double)b.count * kMClasses[b.mclass];
+            // Tile by tile (em_tiles.hip) while the odds and count tables fit one CU's LDS unsliced and W leaves a tile a
+            // stride: sliced handles (their slot layout), tables in global memory (which send short sequences here too) and
+            // "em_tiles" = 0 stay window by window.  The tiles of EVERY sequence, mask or not: getR runs without the mask.
+            if (b.mclass == kLongClass && !global_tables && !sliced && c->use_em_tiles && em_tile_geometry(prm->W, nullptr, &eb.tile_stride)) {
+                std::vector<uint32_t> toff((size_t)b.count + 1, 0u);
+                uint64_t tiles = 0;
+                for (uint32_t t = 0; t < b.count; t++) {
+                    const uint64_t seq = b.h_idx.empty() ? t : b.h_idx[t];
+                    tiles += ((uint64_t)seqs->h_len[seq] - prm->W + eb.tile_stride) / eb.tile_stride;
+                    toff[t + 1] = (uint32_t)std::min<uint64_t>(tiles, UINT32_MAX);
+                }
+                if (tiles != 0 && tiles <= UINT32_MAX) {         // (more tiles than a launch indexes: window by window)
+                    uint32_t* d_toff = nullptr;
+                    if ((rc = em->mem.upload(&d_toff, toff.data(), toff.size())) || (rc = em->mem.alloc(&eb.d_tile_z, (size_t)tiles)) ||
+                        (rc = em->mem.alloc(&eb.d_rec_invz, (size_t)b.count))) return rc;
+                    own_lists = true;                            // (the upload reads a local: synchronised below)
+                    eb.tiled = true; eb.n_tiles = (uint32_t)tiles; eb.d_tile_off = d_toff;
+                }
+            }
             em->ebuckets.push_back(eb);
             prime(eb);
             continue;

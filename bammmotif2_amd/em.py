@@ -554,6 +554,13 @@ class EM:
         check(self.lib.bamm_em_plan_paths(self.h, C.byref(sl), C.byref(ef), C.byref(ln)))
         return bool(sl.value), bool(ef.value), int(ln.value)
 
+    def tile_plan(self) -> dict:
+        """Of plan_paths()' long_seqs: `tiled_seqs` go tile by tile (csrc/em_tiles.hip) in `tiles` tiles, `window_seqs`
+        window by window (bamm_em_tile_plan); decided at creation from the context's `em_tiles` tuning and the model's shape."""
+        out = [C.c_uint64() for _ in range(3)]
+        check(self.lib.bamm_em_tile_plan(self.h, *(C.byref(x) for x in out)))
+        return dict(zip(("tiled_seqs", "tiles", "window_seqs"), (x.value for x in out)))
+
     def close(self):
         if self.h:
             self.lib.bamm_em_destroy(self.h)
@@ -618,6 +625,14 @@ def score_tile_geometry(W: int):
     (bamm_score_tile_geometry: a pure function, no device needed); BammError for a W that leaves no stride."""
     tp, stride = C.c_uint32(), C.c_uint32()
     check(abi.load().bamm_score_tile_geometry(W, C.byref(tp), C.byref(stride)))
+    return tp.value, stride.value
+
+
+def em_tile_geometry(W: int):
+    """(tile_positions, stride) of the tiles an EM pass cuts a sequence beyond 8192 positions into for motifs of width W
+    (bamm_em_tile_geometry: a pure function, no device needed); BammError for a W that leaves no stride."""
+    tp, stride = C.c_uint32(), C.c_uint32()
+    check(abi.load().bamm_em_tile_geometry(W, C.byref(tp), C.byref(stride)))
     return tp.value, stride.value
 
 

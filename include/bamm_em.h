@@ -144,6 +144,10 @@ int  bamm_ctx_set_launch(bamm_ctx* ctx, uint32_t blocks, uint32_t threads_per_bl
  *   "score_tiles"  1/0  the scorer (bamm_logodds*, bamm_occurrences, bamm_fdr_add_set) takes sequences longer than
  *                       BAMM_MAX_SEQ_POSITIONS tile by tile through the register-resident kernel (default 1; 0 = window by
  *                       window, one workgroup per sequence; the same bits); read at the scoring call
+ *   "em_tiles"     1/0  EM passes, getR and bamm_em_sites take sequences longer than BAMM_MAX_SEQ_POSITIONS tile by tile
+ *                       (csrc/em_tiles.hip) while the handle's odds and count tables fit one CU's LDS unsliced (default 1;
+ *                       0 = window by window, one workgroup per sequence: r and counts within a few ulps, see
+ *                       bamm_em_tile_plan); read at bamm_em_create
  *   "scratch_cache_mb" n  idle set-sized scratch blocks (dense r, lists, logs) a context keeps for its next handle
  *                       instead of freeing them (default: a quarter of the device's memory; 0 = keep nothing)
  *   "scratch_poison" 1/0 tests: fill every such block with 0xFF bytes when it is handed out (default 0)
@@ -159,11 +163,13 @@ long long bamm_device_blocks_live(void);
 /* ------------------------------------------------------------------ sequences ----------- */
 /* Uploads sequences [begin,end) of `p`; they stay resident and are shared (ref-counted) by
  * any number of EM handles -- CV folds pass a mask instead of copying (FDR.cpp:49-57).
- * Any length: sequences up to BAMM_MAX_SEQ_POSITIONS go through the register-resident kernels.  Longer ones: EM passes
- * and getR walk them window by window, one workgroup per sequence; the scorer cuts them into overlapping tiles of
- * bamm_score_tile_geometry's size, one wavefront per tile on the whole GPU, while the log-odds table fits the LDS
- * (W * (4^(K+1) + 1) * 4 <= 160 KiB: up to order 5 at usual widths), and walks them window by window beyond that
- * (bamm_score_plan reports the split) -- identical results on every path;
+ * Any length: sequences up to BAMM_MAX_SEQ_POSITIONS go through the register-resident kernels.  Longer ones are cut
+ * into overlapping tiles, one wavefront per tile on the whole GPU: by EM passes, getR and bamm_em_sites while the handle's
+ * tables fit one CU's LDS unsliced (bamm_em_tile_geometry, bamm_em_tile_plan: up to order 3 at usual widths; beyond that
+ * window by window, one workgroup per sequence), and by the scorer (bamm_score_tile_geometry) while the log-odds table
+ * fits the LDS (W * (4^(K+1) + 1) * 4 <= 160 KiB: up to order 5 at usual widths; window by window beyond that,
+ * bamm_score_plan reports the split) -- the scorer's results are identical on every path, the EM's tile path sums a
+ * sequence's partition function in another order (r within 3 ulps of the window-by-window path, deterministic);
  * bamm_seed_from_pwm and bamm_em_mask keep per-wave arrays over one sequence: in LDS up to about
  * 10 000 / 16 000 positions, in a global scratch region per wave beyond (same arithmetic, slower;
  * bamm_em_mask's window lists are 32 bits wide there, and from order 7 on its counts go straight into
@@ -372,9 +378,18 @@ int  bamm_em_plan(bamm_em* em, uint64_t* grouped_seqs, uint64_t* percolumn_seqs,
 int  bamm_em_plan_mixed(bamm_em* em, uint64_t* mixed_seqs);
 /* which of the other paths the handle takes: *sliced = 1 when its tables exceed one CU's LDS and a pass runs column
  * slices (k >= 4 at usual widths); *e_fused = 1 when the E pass of such a handle still holds the whole odds table (r in the
- * reference's layout), 0 when it is sliced as well (r per position slot); *long_seqs = sequences beyond
- * BAMM_MAX_SEQ_POSITIONS, which go window by window (long_seq.hip).  Any pointer may be NULL.               */
+ * reference's layout), 0 when it is sliced as well (r per position slot); *long_seqs = sequences outside the length
+ * classes: beyond BAMM_MAX_SEQ_POSITIONS, or every sequence of a model whose tables stay in global memory (orders >= 7) --
+ * tile by tile or window by window, bamm_em_tile_plan tells which.  Any pointer may be NULL.                   */
 int  bamm_em_plan_paths(bamm_em* em, int* sliced, int* e_fused, uint64_t* long_seqs);
+/* The tiles an EM pass cuts a sequence longer than BAMM_MAX_SEQ_POSITIONS into, for motifs of width W: the scorer's
+ * rule (bamm_score_tile_geometry) with the EM kernels' own positions per lane.  Pure host arithmetic, no device needed;
+ * either pointer may be NULL.  BAMM_ERR_ARG for W = 0 and for a W that leaves no stride of at least 16.              */
+int  bamm_em_tile_geometry(uint32_t W, uint32_t* tile_positions, uint32_t* stride);
+/* Of the handle's long_seqs (bamm_em_plan_paths): *tiled_seqs go tile by tile (csrc/em_tiles.hip), in *tiles tiles
+ * (counted without the sequence mask), *window_seqs window by window (long_seq.hip: sliced handles, tables in global
+ * memory, a W that leaves no stride, "em_tiles" = 0).  Any pointer may be NULL.                                 */
+int  bamm_em_tile_plan(bamm_em* em, uint64_t* tiled_seqs, uint64_t* tiles, uint64_t* window_seqs);
 /* The launch geometry bamm_em_mask computes for a model of width W with Y = 4^(K+1) rows (cells = W * Y) on a set of
  * n_seqs sequences, the longest of max_len positions, on a device of num_cus CUs -- a pure function, exported for tests
  * (no device needed).  out[13]: direct, wave_global, wave_bytes, s_in_lds, e_table, m_cols, m_table, init_table, e_waves,
