@@ -19,15 +19,11 @@ int bamm::dense_r_on_device(bamm_em* em, uint64_t begin, uint64_t end, DevBlocks
         *out = DenseR{em->d_mask_r, 0, false};
         return BAMM_OK;
     }
+    // the E pass the caller last ran (EM.cpp:521), without the fold mask: masked-out sequences still have an r in the reference
+    const EmPass replay = EmPass::read_out();
     if (em->sliced) {
         // the sliced E pass leaves r per position slot p (window start i = p-W+1) in d_state unless it is k_em_seq
-        uint8_t* saved_mask = em->d_mask;
-        em->d_mask = nullptr;                              // masked-out sequences still have an r
-        const uint32_t used = em->events_used, pass_no = em->pass_no;
-        int rc2 = run_accumulate(em, false, true, true);       // dense r
-        em->events_used = used; em->pass_no = pass_no;
-        em->d_mask = saved_mask;
-        if (rc2) return rc2;
+        if (int rc2 = run_accumulate(em, replay)) return rc2;
         *out = DenseR{em->d_state, 0, !em->e_fused};
         return BAMM_OK;
     }
@@ -35,17 +31,12 @@ int bamm::dense_r_on_device(bamm_em* em, uint64_t begin, uint64_t end, DevBlocks
     int rc = tmp.scratch(&d_r, total);
     if (rc) return rc;
     if (hipMemsetAsync(d_r, 0, total * sizeof(float), st) != hipSuccess) { set_error("hipMemsetAsync failed"); return BAMM_ERR_HIP; }
+    const RRange range{d_r, base, (uint32_t)begin, (uint32_t)end};
     for (size_t b = 0; b < em->ebuckets.size() && !rc; b++) {
         const EmBucket& bk = em->ebuckets[b];
-        EmKernelArgs a{};
-        a.sv = make_view(s, em->exc, bk.d_idx, bk.count, nullptr);   // masked-out sequences still have an r in the reference
-        a.K = em->prm.K; a.W = em->prm.W; a.Y = em->Y;
-        a.s = em->s_last; a.q = em->q_last;                 // the E pass the caller last ran (EM.cpp:521)
-        a.acc = nullptr;                                    // responsibilities only
-        a.r_out = d_r; a.r_base = base; a.seq_begin = (uint32_t)begin; a.seq_end = (uint32_t)end;
-        a.fix_scale = 1.0f;
-        if (bk.mclass == kLongClass) { rc = launch_long_bucket(em->ctx, bk, a, false, true, false, false, st); continue; }
-        rc = launch_fused(em, bk, false, true, a, bucket_threads(em->ctx, bk), st);
+        EmKernelArgs a = pass_args(em, bk, replay, &range);
+        if (bk.mclass == kLongClass) rc = launch_long_bucket(em->ctx, bk, a, EmLaunch::r_only(), st);
+        else rc = launch_fused(em, bk, EmLaunch::r_only(), a, bucket_threads(em->ctx, bk), st);
     }
     *out = DenseR{d_r, base, false};
     return rc;
@@ -106,7 +97,7 @@ int bamm_em_create(bamm_ctx* c, bamm_seqs* seqs, const bamm_em_params* prm, cons
     if ((rc = em->mem.alloc(&em->d_status, 8))) return fail(rc);
     if ((rc = em->mem.alloc(&em->d_trace, (size_t)em->prm.max_iterations * 3))) return fail(rc);
     if ((rc = em->mem.alloc(&em->d_iteration, 1))) return fail(rc);
-    em->acc_stride = (em->cells + 3 + 1) & ~(size_t)1;      // slots start on 16-byte boundaries
+    em->acc_stride = (em->acc_words() + 1) & ~(size_t)1;     // slots start on 16-byte boundaries
     if ((rc = em->mem.alloc(&em->d_acc_ring, 3 * em->acc_stride))) return fail(rc);
     em->d_acc = em->d_acc_ring;
     if ((rc = em->mem.alloc(&em->d_v_alt, em->vsz))) return fail(rc);
@@ -116,13 +107,8 @@ int bamm_em_create(bamm_ctx* c, bamm_seqs* seqs, const bamm_em_params* prm, cons
         if ((rc = em->mem.alloc(&em->d_upd_partial, kUpdateMaxBlocks)) || (rc = em->mem.alloc(&em->d_upd_ticket, 1))) return fail(rc);
         if (hipMemsetAsync(em->d_upd_ticket, 0, sizeof(uint32_t), st) != hipSuccess) { set_error("hipMemsetAsync failed"); return fail(BAMM_ERR_HIP); }
     }
-    {   // counts are sums of r * 2^fix_shift over at most n_seqs_global (else this handle's) sequences, each
-        // contributing less than 1 per cell: keep the int64 total below 2^62
-        const uint64_t n_hint = std::max<uint64_t>(prm->n_seqs_bound ? prm->n_seqs_bound : (prm->n_seqs_global ? prm->n_seqs_global : seqs->n), 1);
-        uint32_t bits = 0;
-        while ((uint64_t(1) << bits) < n_hint && bits < 63u) bits++;
-        em->fix_shift = std::min(40u, 62u - std::min(bits, 38u));
-    }
+    // the counts' unit: for the sequences the caller bounds the sum over the ranks by, else this handle's own
+    em->fix_shift = fix_shift_for(std::max<uint64_t>(prm->n_seqs_bound ? prm->n_seqs_bound : (prm->n_seqs_global ? prm->n_seqs_global : seqs->n), 1));
     if (hipMemsetAsync(em->d_n, 0, em->vsz * sizeof(float), st) != hipSuccess ||
         hipMemsetAsync(em->d_status, 0, 8 * sizeof(float), st) != hipSuccess ||
         hipMemsetAsync(em->d_iteration, 0, sizeof(uint32_t), st) != hipSuccess ||
@@ -178,7 +164,7 @@ int bamm_em_estep(bamm_em* em) {
     if (!em) { set_error("null em"); return BAMM_ERR_ARG; }
     if (int vrc = verify_comm(em)) return vrc;
     // s already reflects the current v (made at create / by the last update): E only
-    int rc = run_accumulate(em, false);
+    int rc = run_accumulate(em, EmPass::e_only());
     if (rc) return rc;
     if ((rc = run_allreduce(em))) return rc;
     if ((rc = launch_stat_only(em->d_acc, (uint32_t)em->cells, em->d_status, em->ctx->stream))) return rc;
@@ -193,12 +179,9 @@ int bamm_em_mstep(bamm_em* em) {
     if (!em->estep_done) { set_error("MStep needs the responsibilities of a preceding EStep"); return BAMM_ERR_STATE; }
     // the responsibilities are a pure function of (s, q), both unchanged since the EStep:
     // recompute them on the fly while accumulating counts instead of storing N*L floats
-    const int32_t oq = em->prm.optimize_q;
-    em->prm.optimize_q = 0;                           // EM::MStep never touches q
-    int rc = run_accumulate(em, true, true);          // with the (s, q) the EStep saw, even if q moved since
+    int rc = run_accumulate(em, EmPass::counting().with_last_model());   // with the (s, q) the EStep saw, even if q moved since
     if (!rc) rc = run_allreduce(em);
-    if (!rc) rc = run_update(em, false);
-    em->prm.optimize_q = oq;
+    if (!rc) rc = run_update(em, false);              // outside the q window: EM::MStep never touches q
     return rc;
 }
 
@@ -220,20 +203,20 @@ int bamm_em_optimize_q(bamm_em* em) {
 
 int bamm_em_accumulate(bamm_em* em) {
     if (!em) { set_error("null em"); return BAMM_ERR_ARG; }
-    return run_accumulate(em, true);
+    return run_accumulate(em, EmPass::counting());
 }
 
 int bamm_em_reduce_buffer(bamm_em* em, void** dev_ptr, uint64_t* n_words) {
     if (!em || !dev_ptr || !n_words) { set_error("bad argument"); return BAMM_ERR_ARG; }
     *dev_ptr = em->d_acc;
-    *n_words = em->cells + 3;
+    *n_words = em->acc_words();
     return BAMM_OK;
 }
 
 int bamm_em_set_reduce_buffer(bamm_em* em, void* dev_ptr, uint64_t n_words) {
     if (!em || !dev_ptr) { set_error("bad argument"); return BAMM_ERR_ARG; }
-    if (n_words < em->cells + 3) {
-        set_error("reduce buffer holds %llu 64-bit words, %llu needed", (unsigned long long)n_words, (unsigned long long)(em->cells + 3));
+    if (n_words < em->acc_words()) {
+        set_error("reduce buffer holds %llu 64-bit words, %llu needed", (unsigned long long)n_words, (unsigned long long)em->acc_words());
         return BAMM_ERR_ARG;
     }
     BAMM_HIP(hipSetDevice(em->ctx->device));
@@ -243,7 +226,7 @@ int bamm_em_set_reduce_buffer(bamm_em* em, void* dev_ptr, uint64_t n_words) {
     em->d_acc = static_cast<long long*>(dev_ptr);
     em->acc_external = true;
     em->acc_dirty = false;
-    BAMM_HIP(hipMemsetAsync(em->d_acc, 0, (em->cells + 3) * sizeof(long long), em->ctx->stream));
+    BAMM_HIP(hipMemsetAsync(em->d_acc, 0, em->acc_words() * sizeof(long long), em->ctx->stream));
     return BAMM_OK;
 }
 
@@ -261,7 +244,8 @@ int bamm_em_iterate(bamm_em* em, uint32_t n) {
     // collective per iteration); the last pass's update is a k_update launch, so the handle is in the same state
     // at every API boundary whichever way its updates ran
     for (uint32_t i = 0; i < n; i++) {
-        int rc = run_accumulate(em, true, false, false, (em->fusable && i > 0u) ? (int)(i - 1u < 5u) : -1);
+        const EmPass pass = (em->fusable && i > 0u) ? EmPass::counting().with_fused_update(i - 1u < 5u) : EmPass::counting();
+        int rc = run_accumulate(em, pass);
         if (!rc && i + 1u == n) rc = close_timed_region(em); // a whole-call interval ends behind the last pass's sequence kernel
         if (!rc) rc = run_allreduce(em);
         if (!rc && (!em->fusable || i + 1u == n)) rc = run_update(em, i < 5u);
@@ -311,9 +295,9 @@ int bamm_em_optimize(bamm_em* em, uint32_t* iterations) {
         if (u <= max_it) {
             if (lag && u >= 2u) {
                 em->opt_iteration = u - 1u;
-                r = run_accumulate(em, true, false, false, (int)(u - 1u <= 5u));     // EM.cpp:99 for update(u-1)
+                r = run_accumulate(em, EmPass::counting().with_fused_update(u - 1u <= 5u));     // EM.cpp:99 for update(u-1)
             } else {
-                r = run_accumulate(em, true);
+                r = run_accumulate(em, EmPass::counting());
             }
             if (!r) r = run_allreduce(em);
             if (!r && !lag) { em->opt_iteration = u; r = run_update(em, u <= 5u); }    // EM.cpp:99
@@ -408,7 +392,7 @@ static int mask_buffers(bamm_em* em, const MaskPlan& p, MaskKernelArgs* out) {
     a.q = em->d_q;
     a.q_seq = em->prm.optimize_q ? em->d_mask_qseq : nullptr;
     a.n_total = (float)em->n_active;
-    a.fix_scale = ldexpf(1.0f, (int)em->fix_shift - 40);
+    a.fix_scale = em->fix_scale();
     a.r = em->d_mask_r; a.bits = em->d_mask_bits; a.hist = em->d_mask_hist; a.sel = em->d_mask_sel;
     a.partial_n = em->d_mask_partial_n; a.partial_stat = em->d_mask_partial_stat;
     *out = a;
@@ -484,14 +468,10 @@ int bamm_em_mask(bamm_em* em, float f, uint32_t* iterations, float* cutoff, uint
     if (p.wave_global && (rc = wave_guard.scratch(&a.wave_scratch, p.wave_scratch_bytes))) return rc;
     if ((rc = mask_select(em, p, a, f))) return rc;
 
-    const int32_t oq = em->prm.optimize_q;
-    em->prm.optimize_q = 0;                                  // q is not touched inside the loop
     TimedRegion region(em);
     uint32_t iteration = 0;
     float llh = em->llh_prev;
-    rc = mask_em_loop(em, p, a, &iteration, &llh);
-    em->prm.optimize_q = oq;
-    if (rc) return rc;
+    if ((rc = mask_em_loop(em, p, a, &iteration, &llh))) return rc;   // (its updates run outside the q window: q is not touched inside the loop)
     em->llh_prev = llh;
     em->mask_done = true;
     MaskSelect sel;

@@ -61,8 +61,9 @@ int close_timed_region(bamm_em* em) {
 }
 
 // one bucket through the fused kernel of its flavour (grouped columns or one column at a time)
-int launch_fused(bamm_em* em, const EmBucket& eb, bool accum, bool write_r, EmKernelArgs& a, uint32_t threads,
-                 hipStream_t st, const UpdateArgs* fuse) {
+int launch_fused(bamm_em* em, const EmBucket& eb, EmLaunch what, EmKernelArgs& a, uint32_t threads, hipStream_t st,
+                 const UpdateArgs* fuse) {
+    const bool accum = what.accum, write_r = what.write_r;
     if (!eb.grouped) {
         a.logC = eb.logc;
         a.sparse_cap = accum ? eb.sparse_cap : 0u;
@@ -97,7 +98,7 @@ int launch_fused(bamm_em* em, const EmBucket& eb, bool accum, bool write_r, EmKe
     if (em->peer_on && accum && !write_r) {                  // in-kernel all-reduce in the launch's tail (the pass's only launch)
         em->pass_summed_in_kernel = true;
         comm_peer_args(em->comm, &ga.peer);
-        ga.peer.words = (uint32_t)em->cells + 3u;
+        ga.peer.words = (uint32_t)em->acc_words();
         ga.peer.ticket = em->d_peer_words; ga.peer.err = em->d_peer_words + 1;
         ga.peer.timeout_ticks = (unsigned long long)em->ctx->peer_timeout_ms * 100000ull;      // 100 MHz wall clock
         ga.peer.seq = comm_peer_next_seq(em->comm);          // the ranks count their passes in step
@@ -106,17 +107,26 @@ int launch_fused(bamm_em* em, const EmBucket& eb, bool accum, bool write_r, EmKe
     return launch_em_grp(eb.mclass, accum, write_r, ga, eb.blocks, threads, st);
 }
 
-int launch_long_bucket(const bamm_ctx* c, const EmBucket& bk, const EmKernelArgs& a, bool accum, bool write_r, bool slot_layout,
-                       bool prime_only, hipStream_t st) {
-    if (!bk.tiled) return launch_long_em(a, accum, write_r, slot_layout, prime_only ? kPrimeOnly : bk.blocks, st);
+// `blocks` of the long bucket's kernel (kPrimeOnly: its code object is loaded, nothing runs)
+static int long_bucket_kernel(const EmBucket& bk, const EmKernelArgs& a, EmLaunch what, uint32_t blocks, hipStream_t st) {
+    if (!bk.tiled) return launch_long_em(a, what.accum, what.write_r, what.slot_layout, blocks, st);
     EmTileArgs ta{};
     ta.e = a;
     ta.tile_off = bk.d_tile_off; ta.n_tiles = bk.n_tiles; ta.stride = bk.tile_stride;
     ta.tile_z = bk.d_tile_z; ta.rec_invz = bk.d_rec_invz;
+    return launch_em_tiles(ta, what.accum, what.write_r, blocks, st);
+}
+
+int launch_long_bucket(const bamm_ctx* c, const EmBucket& bk, const EmKernelArgs& a, EmLaunch what, hipStream_t st) {
+    if (!bk.tiled) return long_bucket_kernel(bk, a, what, bk.blocks, st);
     // a block per CU (its count table takes most of the CU's LDS), a wave per tile; nothing in the result depends on it
     const uint32_t waves = em_tile_threads() / 64u;
     const uint32_t blocks = std::min(c->blocks ? c->blocks : (uint32_t)std::max(1, c->num_cus), (bk.n_tiles + waves - 1u) / waves);
-    return launch_em_tiles(ta, accum, write_r, prime_only ? kPrimeOnly : blocks, st);
+    return long_bucket_kernel(bk, a, what, blocks, st);
+}
+
+int prime_long_bucket(const EmBucket& bk, const EmKernelArgs& a, hipStream_t st) {
+    return long_bucket_kernel(bk, a, EmLaunch::of_pass(EmPass::counting()), kPrimeOnly, st);
 }
 
 // clear whatever a pass left unconsumed (accumulate without update, getR replay, a fused sequence cut short)
@@ -127,7 +137,7 @@ int clean_accumulator(bamm_em* em) {
         BAMM_HIP(hipMemsetAsync(em->d_acc_ring, 0, 3 * em->acc_stride * sizeof(long long), st));
         em->acc_cur = 0; em->d_acc = em->d_acc_ring; em->ring_prev_dirty = false;
     } else {
-        BAMM_HIP(hipMemsetAsync(em->d_acc, 0, (em->cells + 3) * sizeof(long long), st));
+        BAMM_HIP(hipMemsetAsync(em->d_acc, 0, em->acc_words() * sizeof(long long), st));
     }
     em->acc_dirty = false;
     return BAMM_OK;
@@ -188,112 +198,130 @@ static void prepare_update(bamm_em* em, bool q_window, bool fused, UpdateArgs& u
     em->books[em->host_iteration & 3u] = em->book();
 }
 
-// local E(+M) pass over every length bucket; every block adds its table into the pass's accumulator.
-// fuse_q_window >= 0: the PREVIOUS pass's model update (with that q-window flag) runs in the block prologue of this
-// pass's first launch instead of a k_update launch of its own (em->fusable handles, accumulating passes only).
-int run_accumulate(bamm_em* em, bool accum, bool replay_last, bool dense_r, int fuse_q_window) {
-    bamm_seqs* s = em->seqs;
+EmKernelArgs pass_args(const bamm_em* em, const EmBucket& bk, const EmPass& p, const RRange* range) {
+    EmKernelArgs a = shape_args(em->prm, em->Y);
+    a.sv = make_view(em->seqs, em->exc, bk.d_idx, bk.count, p.masked ? em->d_mask : nullptr);
+    a.logC = bk.logc;
+    a.s = p.last_model ? em->s_last : em->d_s;
+    a.q = p.last_model ? em->q_last : em->d_q;
+    a.stop = em->stop_arg;                                   // non-null only inside optimize(): no read-out runs there
+    if (range) {
+        // responsibilities only: nothing is accumulated, so no accumulator and no unit (the kernels scale addends nobody
+        // sums by 1); r of the range's sequences goes to a block of the caller's
+        a.acc = nullptr; a.fix_scale = 1.0f;
+        a.r_out = range->r; a.r_base = range->base; a.seq_begin = range->begin; a.seq_end = range->end;
+    } else {
+        // a pass of the handle, the sliced path's replay for getR included: its E-only kernels add their statistics too
+        a.acc = em->d_acc; a.fix_scale = em->fix_scale();
+    }
+    return a;
+}
+
+// Sliced path, one bucket at `waves` waves per block beside the widest M slice's count table: whether a wave's copy of
+// the decoded sequence fits there (the M slices can walk lists), and the longest list of the dense walk that does.
+struct SlicedGeom { bool lists_fit; uint32_t sparse_cap, sparse_wave_bytes; };
+static SlicedGeom sliced_geometry(const std::vector<std::pair<uint32_t, uint32_t>>& m_slices, uint32_t Y, uint32_t logc, uint32_t cap, int M,
+                                  uint32_t waves) {
+    constexpr size_t kLds = 160u * 1024u;
+    uint32_t widest = 0;
+    for (auto& sl : m_slices) widest = std::max(widest, sl.second - sl.first);
+    const size_t table = m_slice_lds_bytes(widest, Y, logc);
+    while (cap && table + waves * m_slice_wave_bytes(M, cap) > kLds) cap -= 64u;
+    return SlicedGeom{m_list_lds_bytes(widest, Y, logc, M, waves) <= kLds, cap, (uint32_t)m_slice_wave_bytes(M, cap)};
+}
+
+enum class SlicedWalk { kDense, kLists };                    // what the E pass hands the M slices: dense r in d_state, or compacted lists
+enum class RunWhen { kAlways, kFewWindows, kManyWindows };   // ... chosen on the device from the previous pass's count of non-zero windows
+
+// one flavour of a sliced bucket's pass: the E pass (k_em_seq with the whole odds table in LDS, or the E slices), then -- in
+// an accumulating pass -- the M slices over what it left
+static int launch_sliced_walk(bamm_em* em, const EmBucket& bk, const EmKernelArgs& a, bool accum, SlicedWalk walk, RunWhen when,
+                              const SlicedGeom& g, uint32_t threads, hipStream_t st) {
+    EmKernelArgs f = a;
+    int r = BAMM_OK;
+    const bool use_lists = walk == SlicedWalk::kLists;
+    f.r_out = em->d_state;
+    if (when != RunWhen::kAlways) {
+        f.nnz_prev = em->d_nnz + em->nnz_prev_slot; f.nnz_limit = em->nnz_limit; f.run_if_long = when == RunWhen::kManyWindows ? 1u : 0u;
+    }
+    if (em->d_nnz && accum) f.nnz_out = em->d_nnz + (em->nnz_prev_slot ^ 1u);
+    if (em->e_fused) {
+        // the whole odds table fits LDS (only the count table does not): the fused kernel's E
+        // pass, leaving r in the reference's layout (k_em_seq WRITE_R) or the lists
+        const EmLaunch e = EmLaunch::r_only();
+        f.seq_end = (uint32_t)em->seqs->n;
+        f.logC = 0; f.sparse_cap = 0; f.sparse_wave_bytes = 0;
+        if (use_lists) { f.list_r = em->d_list_r; f.list_p = em->d_list_p; f.list_n = em->d_list_n; }
+        r = launch_em_seq(bk.mclass, e.accum, e.write_r, f, bk.blocks, threads, st);
+        if (use_lists) {
+            f.logC = em->m_slice_logc;
+            for (size_t i = 0; accum && i < em->m_slices.size() && !r; i++)
+                r = launch_m_list(bk.mclass, f, em->m_slices[i].first, em->m_slices[i].second, bk.blocks, threads, st);
+            return r;
+        }
+    } else {
+        for (size_t i = 0; i < em->e_slices.size() && !r; i++)
+            r = launch_e_slice(bk.mclass, f, em->e_slices[i].first, em->e_slices[i].second, i + 1 == em->e_slices.size(), bk.blocks, threads, st);
+    }
+    f.logC = em->m_slice_logc;
+    f.sparse_cap = g.sparse_cap; f.sparse_wave_bytes = g.sparse_wave_bytes;   // this bucket's list capacity beside the widest slice
+    for (size_t i = 0; accum && i < em->m_slices.size() && !r; i++)
+        r = launch_m_slice(bk.mclass, f, em->m_slices[i].first, em->m_slices[i].second, em->e_fused, bk.blocks, threads, st);
+    return r;
+}
+
+// one bucket of a sliced handle's pass
+static int launch_sliced_bucket(bamm_em* em, const EmBucket& bk, const EmKernelArgs& a, const EmPass& p, uint32_t threads, hipStream_t st) {
+    const SlicedGeom g = sliced_geometry(em->m_slices, em->Y, em->m_slice_logc, em->m_slice_cap, kMClasses[bk.mclass], threads / 64u);
+    // compacted lists instead of dense r between the E pass and the M slices: when the whole odds table is
+    // in LDS (the E pass is k_em_seq) and a wave's copy of the decoded sequence fits beside the count slice
+    const bool lists = em->e_fused && em->d_list_r && !p.dense_r && g.lists_fit;
+    // ... and per pass, decided on the device: while the model is uninformative every window has a non-zero
+    // addend and the list walk costs far more than the dense one (config 4, pass 1: 26.5 against 15.4 ms,
+    // profiles/r03_c4_cold_passes.txt).  Both flavours of the pass are enqueued; the count the previous pass's
+    // E kernel took picks the one that runs (the other's launches return at entry).
+    const bool adaptive = lists && p.accumulate && em->d_nnz && em->adaptive_lists;
+    if ((!lists || adaptive) && !em->d_state)
+        if (int rc = em->mem.scratch(&em->d_state, (size_t)em->seqs->total_len)) return rc;
+    if (!adaptive) return launch_sliced_walk(em, bk, a, p.accumulate, lists ? SlicedWalk::kLists : SlicedWalk::kDense, RunWhen::kAlways, g, threads, st);
+    if (int rc = launch_sliced_walk(em, bk, a, p.accumulate, SlicedWalk::kDense, RunWhen::kManyWindows, g, threads, st)) return rc;   // dense r while the lists would be long
+    return launch_sliced_walk(em, bk, a, p.accumulate, SlicedWalk::kLists, RunWhen::kFewWindows, g, threads, st);
+}
+
+// One pass over every launch of the handle, as `p` describes it; every block adds its table into the pass's accumulator.
+int run_accumulate(bamm_em* em, const EmPass& p) {
     hipStream_t st = em->ctx->stream;
     int rc = use_device(em->ctx);
     if (rc) return rc;
     UpdateArgs fuse{};
     em->pass_summed_in_kernel = false;
-    const bool fusing = fuse_q_window >= 0;
-    if (fusing) prepare_update(em, fuse_q_window != 0, true, fuse);     // consumes the previous pass's sums on the stream
+    const bool fusing = p.fuse != EmPass::kNoFuse;
+    if (fusing) prepare_update(em, p.fuse == EmPass::kFuseQWindow, true, fuse);     // consumes the previous pass's sums on the stream
     else if ((rc = clean_accumulator(em))) return rc;
-    if (em->d_nnz && accum)                                   // sliced path: this pass's count of non-zero windows starts at 0
+    if (em->d_nnz && p.accumulate)                            // sliced path: this pass's count of non-zero windows starts at 0
         BAMM_HIP(hipMemsetAsync(em->d_nnz + (em->nnz_prev_slot ^ 1u), 0, sizeof(unsigned long long), st));
-    if ((rc = record_event(em, true))) return rc;
+    if (p.timed && (rc = record_event(em, true))) return rc;
     for (size_t b = 0; b < em->ebuckets.size(); b++) {
         const EmBucket& bk = em->ebuckets[b];
-        EmKernelArgs a{};
-        a.sv = make_view(s, em->exc, bk.d_idx, bk.count, em->d_mask);
-        a.K = em->prm.K; a.W = em->prm.W; a.Y = em->Y;
-        a.logC = bk.logc;
-        a.s = replay_last ? em->s_last : em->d_s;
-        a.q = replay_last ? em->q_last : em->d_q;
-        a.acc = em->d_acc;
-        a.fix_scale = ldexpf(1.0f, (int)em->fix_shift - 40);
-        a.stop = em->stop_arg;
-        a.r_out = nullptr; a.r_base = 0; a.seq_begin = 0; a.seq_end = 0;
+        EmKernelArgs a = pass_args(em, bk, p);
         if (bk.mclass == kLongClass) {
             // the sliced path's getR() reads dense r from d_state (slot layout unless the E pass is k_em_seq)
-            const bool want_r = em->sliced && dense_r;
-            if (want_r && !em->d_state && (rc = em->mem.scratch(&em->d_state, (size_t)s->total_len))) return rc;
+            EmLaunch what = EmLaunch::of_pass(p);
+            what.write_r = em->sliced && p.dense_r;
+            what.slot_layout = what.write_r && !em->e_fused;
+            if (what.write_r && !em->d_state && (rc = em->mem.scratch(&em->d_state, (size_t)em->seqs->total_len))) return rc;
             a.r_out = em->d_state;
-            if ((rc = launch_long_bucket(em->ctx, bk, a, accum, want_r, want_r && !em->e_fused, false, st))) return rc;
-            continue;
-        }
-        const uint32_t threads = bucket_threads(em->ctx, bk);
-        if (!em->sliced) {
-            rc = launch_fused(em, bk, accum, false, a, threads, st, (fusing && b == 0) ? &fuse : nullptr);
+            rc = launch_long_bucket(em->ctx, bk, a, what, st);
+        } else if (em->sliced) {
+            rc = launch_sliced_bucket(em, bk, a, p, bucket_threads(em->ctx, bk), st);
         } else {
-            uint32_t widest = 0;
-            for (auto& sl : em->m_slices) widest = std::max(widest, sl.second - sl.first);
-            // compacted lists instead of dense r between the E pass and the M slices: when the whole odds table is
-            // in LDS (the E pass is k_em_seq) and a wave's copy of the decoded sequence fits beside the count slice
-            const bool lists = em->e_fused && em->d_list_r && !dense_r &&
-                               m_list_lds_bytes(widest, em->Y, em->m_slice_logc, kMClasses[bk.mclass], threads / 64u) <= 160u * 1024u;
-            // ... and per pass, decided on the device: while the model is uninformative every window has a non-zero
-            // addend and the list walk costs far more than the dense one (config 4, pass 1: 26.5 against 15.4 ms,
-            // profiles/r03_c4_cold_passes.txt).  Both flavours of the pass are enqueued; the count the previous pass's
-            // E kernel took picks the one that runs (the other's launches return at entry).
-            const bool adaptive = lists && accum && em->d_nnz && em->adaptive_lists;
-            if ((!lists || adaptive) && !em->d_state) {
-                if ((rc = em->mem.scratch(&em->d_state, (size_t)s->total_len))) return rc;
-            }
-            auto flavour = [&](bool use_lists, int run_if_long) -> int {   // run_if_long: -1 = unconditional
-                EmKernelArgs f = a;
-                int r = BAMM_OK;
-                f.r_out = em->d_state;
-                if (run_if_long >= 0) {
-                    f.nnz_prev = em->d_nnz + em->nnz_prev_slot; f.nnz_limit = em->nnz_limit; f.run_if_long = (uint32_t)run_if_long;
-                }
-                if (em->d_nnz && accum) f.nnz_out = em->d_nnz + (em->nnz_prev_slot ^ 1u);
-                if (em->e_fused) {
-                    // the whole odds table fits LDS (only the count table does not): the fused kernel's E
-                    // pass, leaving r in the reference's layout (k_em_seq WRITE_R) or the lists
-                    f.seq_end = (uint32_t)s->n;
-                    f.logC = 0; f.sparse_cap = 0; f.sparse_wave_bytes = 0;
-                    if (use_lists) { f.list_r = em->d_list_r; f.list_p = em->d_list_p; f.list_n = em->d_list_n; }
-                    r = launch_em_seq(bk.mclass, false, true, f, bk.blocks, threads, st);
-                    if (use_lists) {
-                        f.logC = em->m_slice_logc;
-                        for (size_t i = 0; accum && i < em->m_slices.size() && !r; i++)
-                            r = launch_m_list(bk.mclass, f, em->m_slices[i].first, em->m_slices[i].second, bk.blocks, threads, st);
-                        return r;
-                    }
-                } else {
-                    for (size_t i = 0; i < em->e_slices.size() && !r; i++)
-                        r = launch_e_slice(bk.mclass, f, em->e_slices[i].first, em->e_slices[i].second,
-                                           i + 1 == em->e_slices.size(), bk.blocks, threads, st);
-                }
-                f.logC = em->m_slice_logc;
-                {   // this bucket's list capacity: what fits next to the widest slice's count table
-                    const size_t table = m_slice_lds_bytes(widest, em->Y, em->m_slice_logc);
-                    uint32_t cap = em->m_slice_cap;
-                    while (cap && table + (threads / 64u) * m_slice_wave_bytes(kMClasses[bk.mclass], cap) > 160u * 1024u) cap -= 64u;
-                    f.sparse_cap = cap;
-                    f.sparse_wave_bytes = (uint32_t)m_slice_wave_bytes(kMClasses[bk.mclass], cap);
-                }
-                for (size_t i = 0; accum && i < em->m_slices.size() && !r; i++)
-                    r = launch_m_slice(bk.mclass, f, em->m_slices[i].first, em->m_slices[i].second, em->e_fused,
-                                       bk.blocks, threads, st);
-                return r;
-            };
-            if (adaptive) {
-                rc = flavour(false, 1);                      // dense r while the lists would be long
-                if (!rc) rc = flavour(true, 0);
-            } else {
-                rc = flavour(lists, -1);
-            }
+            rc = launch_fused(em, bk, EmLaunch::of_pass(p), a, bucket_threads(em->ctx, bk), st, (fusing && b == 0) ? &fuse : nullptr);
         }
         if (rc) return rc;
     }
-    rc = record_event(em, false);
-    if (rc) return rc;
-    if (!replay_last) { em->s_last = em->d_s; em->q_last = em->d_q; em->mask_done = false; }
-    if (em->d_nnz && accum) em->nnz_prev_slot ^= 1u;          // the next pass chooses from what this one counted
+    if (p.timed && (rc = record_event(em, false))) return rc;
+    if (!p.last_model) { em->s_last = em->d_s; em->q_last = em->d_q; em->mask_done = false; }
+    if (em->d_nnz && p.accumulate) em->nnz_prev_slot ^= 1u;   // the next pass chooses from what this one counted
     em->acc_dirty = true;                                     // until the update (or the E-only read-out) has consumed it
     return BAMM_OK;
 }
@@ -314,7 +342,7 @@ int run_allreduce(bamm_em* em) {
     // peer_allreduce_tail).  Every other pass of such a handle -- EStep() alone (an E-only launch has no tail), EM::mask's
     // kernels, a replay -- is summed by the communicator's collective like in mode 1: same integers either way.
     if (em->pass_summed_in_kernel) { em->pass_summed_in_kernel = false; return BAMM_OK; }
-    return allreduce_words(em, em->d_acc, em->cells + 3);
+    return allreduce_words(em, em->d_acc, em->acc_words());
 }
 
 int run_update(bamm_em* em, bool q_window) {
@@ -426,9 +454,7 @@ int verify_comm(bamm_em* em) {
             set_error("the ranks' accumulator units differ (bamm_em_params.n_seqs_bound must be the same on every rank)");
             return BAMM_ERR_ARG;
         }
-        uint32_t bits = 0;
-        while ((uint64_t(1) << bits) < (uint64_t)h[0] && bits < 63u) bits++;
-        if (em->fix_shift > std::min(40u, 62u - std::min(bits, 38u))) {
+        if (em->fix_shift > fix_shift_for((uint64_t)h[0])) {
             set_error("%lld sequences over %u ranks need a coarser accumulator unit than 2^-%u: pass their number as "
                       "bamm_em_params.n_seqs_bound on every rank", h[0], world, em->fix_shift);
             return BAMM_ERR_ARG;
@@ -446,7 +472,7 @@ int verify_comm(bamm_em* em) {
         const EmBucket* eb0 = em->ebuckets.size() == 1u ? &em->ebuckets[0] : nullptr;   // (a shard may plan no launch at all)
         const bool can = eb0 && eb0->grouped && eb0->mclass != kLongClass &&
                          ((eb0->layout & 8u) != 0u || (em->prm.K <= 2u && kMClasses[eb0->mclass] <= BAMM_FUSE_MAX_M)) &&
-                         world <= kPeerMaxWorld && em->cells + 3u <= kStride && !em->allreduce;
+                         world <= kPeerMaxWorld && em->acc_words() <= kStride && !em->allreduce;
         int ready = 0;
         // (every rank goes through the set-up, able or not: it is a collective; the vote inside it counts mapped inboxes)
         int rc = comm_peer_setup(em->comm, kStride, &ready);

@@ -190,7 +190,7 @@ int bamm_fdr_add_set(bamm_fdr* h, int negative, bamm_seqs* set, const uint8_t* s
     if (int rc = fdr_reserve(h, which, total)) return rc;    // refuses a list beyond the sort's index width before anything is scored
     DevBlocks tmp(c);
     DeviceScores sc;
-    int rc = score_on_device(c, set, seq_mask, K, W, bg_order, v, vbg, true, true, tmp, &sc);
+    int rc = score_on_device(c, set, seq_mask, K, W, bg_order, v, vbg, kWantMops, kPooledMops, tmp, &sc);
     if (rc) return rc;
     float* dst = h->d[which] + h->n[which];
     if (!seq_mask) {

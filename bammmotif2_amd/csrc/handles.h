@@ -12,6 +12,7 @@
 #pragma once
 
 #include <algorithm>
+#include <cmath>
 #include <mutex>
 #include <thread>
 #include <unordered_map>
@@ -99,6 +100,46 @@ struct EmBook {
     bool mask_done = false;                     // getR() serves d_mask_r
     bool ring_prev_dirty = false;               // the ring slot behind acc_cur was read by a fused update and awaits clearing
 };
+
+// The finest unit 2^-shift the counts of `n` sequences may travel in: a cell is a sum of r * 2^shift over them, each
+// contributing less than 1, and the int64 total (summed over the ranks as well) stays below 2^62.
+inline uint32_t fix_shift_for(uint64_t n) {
+    uint32_t bits = 0;
+    while ((uint64_t(1) << bits) < n && bits < 63u) bits++;
+    return std::min(40u, 62u - std::min(bits, 38u));
+}
+
+// What one pass over the handle's launches is (run_accumulate); a call site names the fields it sets.
+struct EmPass {
+    enum Fuse { kNoFuse, kFuse, kFuseQWindow };
+    bool accumulate = false;     // the kernels add counts (else responsibilities' statistics only: EStep, a read-out)
+    bool last_model = false;     // with (s_last, q_last), what the last E pass used, instead of the current (d_s, d_q); such a
+                                 // pass leaves s_last / q_last / mask_done as they are
+    bool dense_r = false;        // sliced path: leaves dense r in d_state (getR, bamm_em_sites)
+    bool masked = true;          // the fold mask applies (a read-out reports masked-out sequences too)
+    bool timed = true;           // a pass of its iterate() / optimize() call: counted in pass_no, bracketed by events as the
+                                 // timing mode says (record_event); an untimed pass records nothing and opens no region
+    Fuse fuse = kNoFuse;         // the PREVIOUS pass's model update runs in the prologue of this pass's first launch instead of
+                                 // a k_update launch (fusable handles, accumulating passes), with or without the q window
+    static EmPass e_only() { return EmPass{}; }
+    static EmPass counting() { EmPass p; p.accumulate = true; return p; }
+    // the E pass the caller last ran, once more, for its r: every sequence, outside the call's timing
+    static EmPass read_out() { EmPass p; p.last_model = true; p.dense_r = true; p.masked = false; p.timed = false; return p; }
+    EmPass with_last_model() const { EmPass p = *this; p.last_model = true; return p; }
+    EmPass with_fused_update(bool q_window) const { EmPass p = *this; p.fuse = q_window ? kFuseQWindow : kFuse; return p; }
+};
+
+// What one launch of a bucket does (launch_fused, launch_long_bucket and the kernels' own launchers).
+struct EmLaunch {
+    bool accum = false;          // adds counts
+    bool write_r = false;        // stores r
+    bool slot_layout = false;    // ... window start i at slot i+W-1 (long bucket of a sliced handle whose E pass is k_e_slice)
+    static EmLaunch of_pass(const EmPass& p) { EmLaunch l; l.accum = p.accumulate; return l; }
+    static EmLaunch r_only() { EmLaunch l; l.write_r = true; return l; }
+};
+
+// A read-out of sequences [begin,end) into r (r[0] = position `base` of the set) instead of a pass of the handle.
+struct RRange { float* r; uint64_t base; uint32_t begin, end; };
 
 }  // namespace bamm
 
@@ -245,6 +286,8 @@ struct bamm_em : bamm::EmBook {                 // (the fields an update moves: 
     uint32_t* d_upd_ticket = nullptr;           // ... and the word its blocks draw tickets from
     bool acc_external = false;                 // caller-owned (bamm_em_set_reduce_buffer)
     uint32_t fix_shift = 40;                   // counts travel in units of 2^-fix_shift (40 unless the set is huge)
+    float fix_scale() const { return ldexpf(1.0f, (int)fix_shift - 40); }   // ... what the kernels multiply their 2^40-based addends by
+    size_t acc_words() const { return cells + 3; }                          // one accumulator slot: [cells | llh | sum_r | n_seqs]
     float* h_status = nullptr;                  // pinned, 8 floats (+ 2 x 8 for optimize()'s look-ahead where the mirror below is missing)
     unsigned long long* h_tagged = nullptr;     // ... + 2 x 8 tagged words behind them: what the updates of optimize() report (UpdateArgs::status_mirror)
     unsigned long long* d_status_mirror = nullptr;   // h_tagged as the device addresses it
@@ -363,6 +406,7 @@ struct DeviceScores {
 };
 int score_on_device(bamm_ctx* c, bamm_seqs* s, const uint8_t* seq_mask, uint32_t K, uint32_t W, uint32_t bg_order, const float* v,
                     const float* vbg, bool want_mops, bool pooled_mops, DevBlocks& tmp, DeviceScores* out);
+constexpr bool kWantMops = true, kPooledMops = true;         // what the callers that keep every window's score on the device pass
 
 // ---- plan.cpp ----
 uint32_t default_threads(const bamm_ctx* c, int mclass);
@@ -417,14 +461,18 @@ struct TimedRegion {
     explicit TimedRegion(bamm_em* e) : em(e) { em->events_used = 0; em->pass_no = 0; em->region_open = false; }
     ~TimedRegion() { (void)close_timed_region(em); }
 };
-int launch_fused(bamm_em* em, const EmBucket& eb, bool accum, bool write_r, EmKernelArgs& a, uint32_t threads,
-                 hipStream_t st, const UpdateArgs* fuse = nullptr);
+// the shape fields every EmKernelArgs starts from (a handle's launches; the priming threads, which have no handle)
+inline EmKernelArgs shape_args(const bamm_em_params& prm, uint32_t Y) { EmKernelArgs a{}; a.K = prm.K; a.W = prm.W; a.Y = Y; return a; }
+// the arguments of bucket `bk` in pass `p`, or (range) in a read-out of r over a range: the one place they are filled
+EmKernelArgs pass_args(const bamm_em* em, const EmBucket& bk, const EmPass& p, const RRange* range = nullptr);
+int launch_fused(bamm_em* em, const EmBucket& eb, EmLaunch what, EmKernelArgs& a, uint32_t threads, hipStream_t st,
+                 const UpdateArgs* fuse = nullptr);
 int clean_accumulator(bamm_em* em);
-int run_accumulate(bamm_em* em, bool accum, bool replay_last = false, bool dense_r = false, int fuse_q_window = -1);
-// The one way a bucket of mclass kLongClass is launched -- by a pass, by getR / bamm_em_sites, and to load its code object
-// (prime_only: nothing is launched) alike: tile by tile when the plan says so (EmBucket::tiled), else window by window.
-int launch_long_bucket(const bamm_ctx* c, const EmBucket& bk, const EmKernelArgs& a, bool accum, bool write_r, bool slot_layout,
-                       bool prime_only, hipStream_t st);
+int run_accumulate(bamm_em* em, const EmPass& p);
+// The one way a bucket of mclass kLongClass is launched, by a pass and by getR / bamm_em_sites alike: tile by tile when the
+// plan says so (EmBucket::tiled), else window by window.  prime_long_bucket loads the same kernel's code object and launches nothing.
+int launch_long_bucket(const bamm_ctx* c, const EmBucket& bk, const EmKernelArgs& a, EmLaunch what, hipStream_t st);
+int prime_long_bucket(const EmBucket& bk, const EmKernelArgs& a, hipStream_t st);
 int allreduce_words(bamm_em* em, void* dev_ptr, size_t n_words);
 int run_allreduce(bamm_em* em);
 float* q_write_slot(bamm_em* em);

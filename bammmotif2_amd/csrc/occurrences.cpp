@@ -44,7 +44,7 @@ int bamm_occurrences(bamm_ctx* c, bamm_seqs* positives, bamm_seqs* negatives, ui
     // write unconditionally: a few bytes per sequence nobody reads here)
     DevBlocks tmp(c);
     DeviceScores neg;
-    if ((rc = score_on_device(c, negatives, nullptr, K, W, bg_order, v, vbg, true, true, tmp, &neg))) return rc;
+    if ((rc = score_on_device(c, negatives, nullptr, K, W, bg_order, v, vbg, kWantMops, kPooledMops, tmp, &neg))) return rc;
     {
         // the sort's second buffer goes back to the pool as soon as the launches are queued: whoever takes it next (the
         // positives' scores below) is ordered behind them on the context's one stream.  The small histogram table is a
@@ -67,7 +67,7 @@ int bamm_occurrences(bamm_ctx* c, bamm_seqs* positives, bamm_seqs* negatives, ui
     DeviceScores pos;
     pos.moff.assign(1, 0);
     if (positives->n) {
-        if ((rc = score_on_device(c, positives, nullptr, K, W, bg_order, v, vbg, true, true, tmp, &pos))) return rc;
+        if ((rc = score_on_device(c, positives, nullptr, K, W, bg_order, v, vbg, kWantMops, kPooledMops, tmp, &pos))) return rc;
         const uint64_t n_pos = pos.moff[positives->n];
         OccRankArgs a{};
         a.pos = pos.mops; a.n_pos = n_pos; a.neg = neg.mops; a.n_neg = (uint32_t)negN; a.p_cutoff = p_cutoff;

@@ -18,20 +18,22 @@ constexpr size_t kLds = 160 * 1024;
 // otherwise lands in the handle's first pass.  Runs on a thread of its own beside bamm_em_create's host work.
 int prime_bucket(bamm_ctx* c, const bamm_em_params& prm, uint32_t Y, bool sliced, const EmBucket& eb) {
     if (hipSetDevice(c->device) != hipSuccess) { set_error("hipSetDevice failed"); return BAMM_ERR_HIP; }
-    EmKernelArgs a{};
-    a.K = prm.K; a.W = prm.W; a.Y = Y;
-    if (eb.mclass == kLongClass) return launch_long_bucket(c, eb, a, true, false, false, true, c->stream);
+    // (no handle here -- bamm_em_create may have failed and deleted it by now -- so only the shape of pass_args)
+    EmKernelArgs a = shape_args(prm, Y);
+    if (eb.mclass == kLongClass) return prime_long_bucket(eb, a, c->stream);
     const uint32_t threads = bucket_threads(c, eb);
+    EmLaunch what;
     if (sliced || !eb.grouped) {                             // k_em_seq, the slices and the list walk share kernels.hip
         a.logC = 0;
-        return launch_em_seq(eb.mclass, false, false, a, kPrimeOnly, threads, c->stream);
+        return launch_em_seq(eb.mclass, what.accum, what.write_r, a, kPrimeOnly, threads, c->stream);
     }
+    what.accum = true;
     GrpKernelArgs ga{};
     ga.e = a;
     if (!grp_geometry(prm.K, prm.W, eb.G, kMClasses[eb.mclass], threads / 64u, true, eb.logc, eb.layout, &ga.g)) return BAMM_OK;   // (the launch reports it)
     if (eb.layout & 8u)                                      // mixed rows: the builder of the lane records is the handle's first launch
         if (int rc = launch_mix_records(eb.mclass, SeqView{}, nullptr, prm.W, ga.g.T, ga.g.mixB, 0u, nullptr, kPrimeOnly, c->stream)) return rc;
-    return launch_em_grp(eb.mclass, true, false, ga, kPrimeOnly, threads, c->stream);
+    return launch_em_grp(eb.mclass, what.accum, what.write_r, ga, kPrimeOnly, threads, c->stream);
 }
 
 }  // namespace
@@ -101,136 +103,138 @@ bool plan_slices(bamm_em* em) {
     return global_tables;
 }
 
-int plan_launches(bamm_em* em, bool global_tables, const uint8_t* seq_mask, Primers& primers) {
-    const bamm_em_params* prm = &em->prm;
-    bamm_ctx* c = em->ctx;
-    bamm_seqs* seqs = em->seqs;
-    const uint32_t Y = em->Y;
-    const bool sliced = em->sliced;
-    hipStream_t st = c->stream;
-    int rc = BAMM_OK;
-    // the code objects of the kernels the handle will launch are loaded beside the host work below (prime_bucket), each as
-    // soon as the plan names the kernel
-    auto prime = [&primers, c, prm_copy = em->prm, Y, sliced](const EmBucket& eb) {
-        primers.t.emplace_back([c, prm_copy, Y, sliced, eb] { (void)prime_bucket(c, prm_copy, Y, sliced, eb); });
-    };
-    // launches of one pass: every length bucket, split into the sequences the grouped-column kernel
-    // takes (no exception, or all of them within its virtual rows) and the rest
-    const bool want_grouped = !sliced && prm->K <= 3u && c->use_grouped;
-    // A shard of a sharded set plans its kernels as the whole set would: which rows a sequence is multiplied through
-    // (mixed or uniform) decides the last bit of its responsibilities, so the choice follows the GLOBAL size the caller
-    // names (n_seqs_bound / n_seqs_global; this shard's own count when it names neither) and nothing about the shard:
-    // every length class of a set of `plan_n` sequences is planned as a launch of that many (a class that holds a small
-    // part of a large set pays the larger tables' few microseconds per launch; an estimate of the class's global share
-    // from this shard's own mix of lengths could differ between ranks next to the threshold).  The other input of the
-    // plan, whether most sequences of a class carry exceptions, is the shard's own: a property of the data that holds
-    // for every shard alike on double-stranded sets (each sequence has its strand junction) and on clean single-stranded ones.
-    const uint64_t plan_n = std::max<uint64_t>(std::max<uint64_t>(prm->n_seqs_bound, prm->n_seqs_global), seqs->n);
-    bool own_lists = false;                                  // index lists were made for this handle (capable / other split)
-    for (auto& b : seqs->buckets) {
-        if (b.mclass == kLongClass || global_tables) {       // beyond the length classes / tables beyond LDS: long_seq.hip
-            EmBucket eb;
-            eb.mclass = kLongClass; eb.count = b.count; eb.d_idx = b.d_idx;
-            eb.work = b.mclass == kLongClass ? b.work : (double)b.count * kMClasses[b.mclass];
-            // Tile by tile (em_tiles.hip) while the odds and count tables fit one CU's LDS unsliced and W leaves a tile a
-            // stride: sliced handles (their slot layout), tables in global memory (which send short sequences here too) and
-            // "em_tiles" = 0 stay window by window.  The tiles of EVERY sequence, mask or not: getR runs without the mask.
-            if (b.mclass == kLongClass && !global_tables && !sliced && c->use_em_tiles && em_tile_geometry(prm->W, nullptr, &eb.tile_stride)) {
-                std::vector<uint32_t> toff((size_t)b.count + 1, 0u);
-                uint64_t tiles = 0;
-                for (uint32_t t = 0; t < b.count; t++) {
-                    const uint64_t seq = b.h_idx.empty() ? t : b.h_idx[t];
-                    tiles += ((uint64_t)seqs->h_len[seq] - prm->W + eb.tile_stride) / eb.tile_stride;
-                    toff[t + 1] = (uint32_t)std::min<uint64_t>(tiles, UINT32_MAX);
-                }
-                if (tiles != 0 && tiles <= UINT32_MAX) {         // (more tiles than a launch indexes: window by window)
-                    uint32_t* d_toff = nullptr;
-                    if ((rc = em->mem.upload(&d_toff, toff.data(), toff.size())) || (rc = em->mem.alloc(&eb.d_tile_z, (size_t)tiles)) ||
-                        (rc = em->mem.alloc(&eb.d_rec_invz, (size_t)b.count))) return rc;
-                    own_lists = true;                            // (the upload reads a local: synchronised below)
-                    eb.tiled = true; eb.n_tiles = (uint32_t)tiles; eb.d_tile_off = d_toff;
-                }
-            }
-            em->ebuckets.push_back(eb);
-            prime(eb);
-            continue;
-        }
-        const int Mcls = kMClasses[b.mclass];
-        const uint32_t threads = default_threads(c, b.mclass);
-        GrpGeom gg{};
-        uint32_t glogc = 0, gG = 0;
-        const ExcK::XRec* xr = nullptr;
-        std::vector<uint32_t> yes, no;
-        uint32_t glayout = 0;
-        // do most sequences of this bucket carry exceptions (a double-stranded set: all of them)?
-        std::atomic<size_t> with_exc_a{0};
-        host_ranges(b.count, [&](uint64_t i0, uint64_t i1) {
-            size_t cnt = 0;
-            for (uint64_t i = i0; i < i1; i++) {
-                const uint32_t n = b.d_idx ? b.h_idx[i] : (uint32_t)i;
-                cnt += em->exc->h_off[n + 1] != em->exc->h_off[n];
-            }
-            with_exc_a.fetch_add(cnt, std::memory_order_relaxed);
-        });
-        const size_t with_exc = with_exc_a.load();
-        if (want_grouped && grp_supported_class(Mcls, prm->K) &&
-            grp_plan(prm->K, prm->W, Mcls, std::min(threads, grp_max_threads(Mcls)) / 64u, 2 * with_exc > b.count, plan_n * (uint64_t)Mcls >= 40000ull * 7ull, c->group_size, c->group_layout, &gG, &glogc, &glayout) &&
-            grp_geometry(prm->K, prm->W, gG, Mcls, std::min(threads, grp_max_threads(Mcls)) / 64u, true, glogc, glayout, &gg)) {
-            { EmBucket pb; pb.mclass = b.mclass; pb.grouped = true; pb.logc = glogc; pb.G = gG; pb.layout = glayout; prime(pb); }
-            if ((rc = xrec_for_group(seqs, prm->K, gG, em->exc, &xr))) return rc;
-            // exceptions within the virtual rows for them, and clear of the rows for the LW1 edge
-            auto capable = [&](uint32_t n) {
-                const uint32_t B = xr->h_B[n];
-                return B == 0u || (B <= gg.Bj && (gg.np != 0u || xr->h_lo[n] + B + gg.G <= seqs->h_len[n] - prm->W + 1u));
-            };
-            std::atomic<bool> all_capable{true};
-            host_ranges(b.count, [&](uint64_t i0, uint64_t i1) {
-                for (uint64_t i = i0; i < i1 && all_capable.load(std::memory_order_relaxed); i++)
-                    if (!capable(b.d_idx ? b.h_idx[i] : (uint32_t)i)) all_capable.store(false, std::memory_order_relaxed);
-            });
-            const bool all = all_capable.load();
-            if (!all)
-                for (uint32_t i = 0; i < b.count; i++) {
-                    const uint32_t n = b.d_idx ? b.h_idx[i] : i;
-                    (capable(n) ? yes : no).push_back(n);
-                }
-            EmBucket eb;
-            eb.mclass = b.mclass; eb.grouped = true; eb.logc = glogc; eb.G = gG; eb.layout = glayout; eb.d_xrec = xr->d_xrec;
-            if (all) { eb.count = b.count; eb.d_idx = b.d_idx; }
-            else {
-                uint32_t* d = nullptr;
-                if ((rc = em->mem.upload(&d, yes.data(), yes.size()))) return rc;
-                own_lists = true;
-                eb.count = (uint32_t)yes.size(); eb.d_idx = d;
-            }
-            if ((glayout & 8u) && eb.count) {
-                // mixed rows: every lane's stream window and fix-lane codes per launch slot of this bucket, derived once
-                // here instead of in every pass (lane_records.h; 512 bytes per sequence, set-sized: from the scratch pool);
-                // gg is the accumulating layout: its resident columns decide what a fix lane has left to log
-                uint2* rec = nullptr;
-                if ((rc = em->mem.scratch(&rec, (size_t)eb.count * 64u))) return rc;
-                if ((rc = launch_mix_records(eb.mclass, make_view(seqs, em->exc, eb.d_idx, eb.count, nullptr), xr->d_xrec, prm->W,
-                                             gg.T, gg.mixB, mix_resident_cols(gg), rec, (uint32_t)std::max(1, c->num_cus), st))) return rc;
-                eb.d_lane_rec = rec;
-            }
-            eb.work = (double)eb.count * Mcls * 0.6;       // grouped passes cost about 60 % per sequence
-            if (eb.count) em->ebuckets.push_back(eb);
-            if (all) continue;
-        }
-        EmBucket eb;
-        eb.mclass = b.mclass;
-        if (!no.empty()) {
-            uint32_t* d = nullptr;
-            if ((rc = em->mem.upload(&d, no.data(), no.size()))) return rc;
-            own_lists = true;
-            eb.count = (uint32_t)no.size(); eb.d_idx = d;
-        } else { eb.count = b.count; eb.d_idx = b.d_idx; }
-        eb.work = (double)eb.count * Mcls;
-        em->ebuckets.push_back(eb);
-        prime(eb);
+namespace {
+
+// What the stages of plan_launches share.  The code objects of the kernels the handle will launch are loaded beside the
+// host work (prime_bucket, on a thread of its own), each as soon as the plan names the kernel.
+struct Planning {
+    bamm_em* em;
+    Primers& primers;
+    bool uploads_pending = false;                            // index lists / tile offsets were uploaded: one synchronisation at the end
+    void prime(const EmBucket& eb) {
+        primers.t.emplace_back([c = em->ctx, prm = em->prm, Y = em->Y, sliced = em->sliced, eb] { (void)prime_bucket(c, prm, Y, sliced, eb); });
     }
-    if (own_lists && hipStreamSynchronize(st) != hipSuccess) { set_error("stream sync failed"); return BAMM_ERR_HIP; }
-    // launch geometry: blocks split over the launches in proportion to their work
+};
+
+// Stage 1, a bucket beyond the length classes (or any bucket of a handle whose tables stay in global memory): one launch of
+// long_seq.hip, or of em_tiles.hip.  Decides tiled or window by window; a tiled bucket uploads its tile offsets and allocates
+// the tiles' and records' normalisers.
+int plan_long_bucket(Planning& pl, const Bucket& b, bool global_tables, EmBucket* out) {
+    bamm_em* em = pl.em;
+    const uint32_t W = em->prm.W;
+    EmBucket eb;
+    eb.mclass = kLongClass; eb.count = b.count; eb.d_idx = b.d_idx;
+    eb.work = b.mclass == kLongClass ? b.work : (double)b.count * kMClasses[b.mclass];
+    // Tile by tile (em_tiles.hip) while the odds and count tables fit one CU's LDS unsliced and W leaves a tile a
+    // stride: sliced handles (their slot layout), tables in global memory (which send short sequences here too) and
+    // "em_tiles" = 0 stay window by window.  The tiles of EVERY sequence, mask or not: getR runs without the mask.
+    if (b.mclass == kLongClass && !global_tables && !em->sliced && em->ctx->use_em_tiles && em_tile_geometry(W, nullptr, &eb.tile_stride)) {
+        std::vector<uint32_t> toff((size_t)b.count + 1, 0u);
+        uint64_t tiles = 0;
+        for (uint32_t t = 0; t < b.count; t++) {
+            const uint64_t seq = b.h_idx.empty() ? t : b.h_idx[t];
+            tiles += ((uint64_t)em->seqs->h_len[seq] - W + eb.tile_stride) / eb.tile_stride;
+            toff[t + 1] = (uint32_t)std::min<uint64_t>(tiles, UINT32_MAX);
+        }
+        if (tiles != 0 && tiles <= UINT32_MAX) {             // (more tiles than a launch indexes: window by window)
+            uint32_t* d_toff = nullptr;
+            int rc;
+            if ((rc = em->mem.upload(&d_toff, toff.data(), toff.size())) || (rc = em->mem.alloc(&eb.d_tile_z, (size_t)tiles)) ||
+                (rc = em->mem.alloc(&eb.d_rec_invz, (size_t)b.count))) return rc;
+            pl.uploads_pending = true;
+            eb.tiled = true; eb.n_tiles = (uint32_t)tiles; eb.d_tile_off = d_toff;
+        }
+    }
+    *out = eb;
+    return BAMM_OK;
+}
+
+// `ids` as a launch's index list on the device (owned by the handle)
+int upload_ids(Planning& pl, const std::vector<uint32_t>& ids, EmBucket* eb) {
+    uint32_t* d = nullptr;
+    if (int rc = pl.em->mem.upload(&d, ids.data(), ids.size())) return rc;
+    pl.uploads_pending = true;
+    eb->count = (uint32_t)ids.size(); eb->d_idx = d;
+    return BAMM_OK;
+}
+
+// Stage 2, one length class: the sequences the grouped-column kernel takes (no exception, or all of them within its
+// virtual rows) and the rest, appended to `out` as one or two launches.  Decides group size / copies / layout (grp_plan);
+// uploads the index lists of a split class and, for mixed rows, allocates and builds (one launch) the lane records.
+int plan_class_split(Planning& pl, const Bucket& b, bool want_grouped, uint64_t plan_n, std::vector<EmBucket>& out) {
+    bamm_em* em = pl.em;
+    bamm_seqs* seqs = em->seqs;
+    const bamm_ctx* c = em->ctx;
+    const uint32_t K = em->prm.K, W = em->prm.W;
+    const int Mcls = kMClasses[b.mclass];
+    const uint32_t waves = std::min(default_threads(c, b.mclass), grp_max_threads(Mcls)) / 64u;   // of the grouped kernel
+    auto seq_at = [&](uint64_t i) { return b.d_idx ? b.h_idx[i] : (uint32_t)i; };
+    int rc;
+    // do most sequences of this bucket carry exceptions (a double-stranded set: all of them)?
+    std::atomic<size_t> with_exc{0};
+    host_ranges(b.count, [&](uint64_t i0, uint64_t i1) {
+        size_t cnt = 0;
+        for (uint64_t i = i0; i < i1; i++) cnt += em->exc->h_off[seq_at(i) + 1] != em->exc->h_off[seq_at(i)];
+        with_exc.fetch_add(cnt, std::memory_order_relaxed);
+    });
+    GrpGeom gg{};
+    uint32_t glogc = 0, gG = 0, glayout = 0;
+    std::vector<uint32_t> yes, no;
+    if (want_grouped && grp_supported_class(Mcls, K) &&
+        grp_plan(K, W, Mcls, waves, 2 * with_exc.load() > b.count, plan_n * (uint64_t)Mcls >= 40000ull * 7ull, c->group_size, c->group_layout, &gG, &glogc, &glayout) &&
+        grp_geometry(K, W, gG, Mcls, waves, true, glogc, glayout, &gg)) {
+        EmBucket eb;
+        eb.mclass = b.mclass; eb.grouped = true; eb.logc = glogc; eb.G = gG; eb.layout = glayout;
+        pl.prime(eb);
+        const ExcK::XRec* xr = nullptr;
+        if ((rc = xrec_for_group(seqs, K, gG, em->exc, &xr))) return rc;
+        eb.d_xrec = xr->d_xrec;
+        // exceptions within the virtual rows for them, and clear of the rows for the LW1 edge
+        auto capable = [&](uint32_t n) {
+            const uint32_t B = xr->h_B[n];
+            return B == 0u || (B <= gg.Bj && (gg.np != 0u || xr->h_lo[n] + B + gg.G <= seqs->h_len[n] - W + 1u));
+        };
+        std::atomic<bool> all_capable{true};
+        host_ranges(b.count, [&](uint64_t i0, uint64_t i1) {
+            for (uint64_t i = i0; i < i1 && all_capable.load(std::memory_order_relaxed); i++)
+                if (!capable(seq_at(i))) all_capable.store(false, std::memory_order_relaxed);
+        });
+        const bool all = all_capable.load();
+        if (all) { eb.count = b.count; eb.d_idx = b.d_idx; }
+        else {
+            for (uint32_t i = 0; i < b.count; i++) (capable(seq_at(i)) ? yes : no).push_back(seq_at(i));
+            if ((rc = upload_ids(pl, yes, &eb))) return rc;
+        }
+        if ((glayout & 8u) && eb.count) {
+            // mixed rows: every lane's stream window and fix-lane codes per launch slot of this bucket, derived once
+            // here instead of in every pass (lane_records.h; 512 bytes per sequence, set-sized: from the scratch pool);
+            // gg is the accumulating layout: its resident columns decide what a fix lane has left to log
+            uint2* rec = nullptr;
+            if ((rc = em->mem.scratch(&rec, (size_t)eb.count * 64u))) return rc;
+            if ((rc = launch_mix_records(eb.mclass, make_view(seqs, em->exc, eb.d_idx, eb.count, nullptr), xr->d_xrec, W,
+                                         gg.T, gg.mixB, mix_resident_cols(gg), rec, (uint32_t)std::max(1, c->num_cus), c->stream))) return rc;
+            eb.d_lane_rec = rec;
+        }
+        eb.work = (double)eb.count * Mcls * 0.6;             // grouped passes cost about 60 % per sequence
+        if (eb.count) out.push_back(eb);
+        if (all) return BAMM_OK;
+    }
+    EmBucket eb;
+    eb.mclass = b.mclass;
+    if (no.empty()) { eb.count = b.count; eb.d_idx = b.d_idx; }
+    else if ((rc = upload_ids(pl, no, &eb))) return rc;
+    eb.work = (double)eb.count * Mcls;
+    out.push_back(eb);
+    pl.prime(eb);
+    return BAMM_OK;
+}
+
+// Stage 3, every launch: its blocks (split over the launches in proportion to their work) and, for the per-column kernel,
+// the copies of the count table and the sparse M-step's scratch.  Decides only; fills the EmBuckets and total_blocks.
+void plan_launch_sizes(bamm_em* em) {
+    const bamm_ctx* c = em->ctx;
+    const uint32_t W = em->prm.W, Y = em->Y;
+    const bool sliced = em->sliced;
     double total_work = 0;
     for (auto& b : em->ebuckets) total_work += b.work;
     em->total_blocks = 0;
@@ -251,14 +255,14 @@ int plan_launches(bamm_em* em, bool global_tables, const uint8_t* seq_mask, Prim
             size_t scratch = sliced ? 0 : sparse_wave_bytes(Mcls) * (threads / 64u);
             uint32_t cap = sliced ? 0u : sparse_cap_for(Mcls);
             if (!c->use_sparse) { cap = 0; scratch = 0; }
-            if (cap && (em_lds_bytes(prm->W, Y, true, 0, scratch) > kLds / blocks_per_cu ||
-                        pick_log_copies(prm->W, Y, blocks_per_cu, scratch) + 1 < pick_log_copies(prm->W, Y, blocks_per_cu, 0))) {
+            if (cap && (em_lds_bytes(W, Y, true, 0, scratch) > kLds / blocks_per_cu ||
+                        pick_log_copies(W, Y, blocks_per_cu, scratch) + 1 < pick_log_copies(W, Y, blocks_per_cu, 0))) {
                 cap = 0;
                 scratch = 0;
             }
             b.sparse_cap = cap;
             b.sparse_bytes = (uint32_t)(cap ? sparse_wave_bytes(Mcls) : 0);
-            b.logc = sliced ? 0u : pick_log_copies(prm->W, Y, blocks_per_cu, scratch);
+            b.logc = sliced ? 0u : pick_log_copies(W, Y, blocks_per_cu, scratch);
         }
         const uint32_t per_cu = b.grouped ? 1u : blocks_per_cu;
         const uint32_t all = c->blocks ? c->blocks : (uint32_t)std::max(1, c->num_cus) * per_cu;
@@ -269,47 +273,86 @@ int plan_launches(bamm_em* em, bool global_tables, const uint8_t* seq_mask, Prim
         b.blocks = nb;
         em->total_blocks += nb;
     }
-    // fused updates (update_kernel.h): inside iterate() / optimize() the model update of pass p runs in the block
-    // prologue of pass p+1's FIRST launch -- a grouped kernel whose count tables leave room for the update's scratch
-    if (!sliced && c->use_fused_update && update_fits_lds(prm->K, prm->W) && prm->K <= 2u) {
-        size_t best = em->ebuckets.size();
-        for (size_t i = 0; i < em->ebuckets.size(); i++)
-            if (em->ebuckets[i].grouped && kMClasses[em->ebuckets[i].mclass] <= BAMM_FUSE_MAX_M &&   // the classes built with the fused prologue
-                (best == em->ebuckets.size() || em->ebuckets[i].count > em->ebuckets[best].count)) best = i;
-        if (best < em->ebuckets.size()) {
-            std::swap(em->ebuckets[0], em->ebuckets[best]);
-            const EmBucket& eb = em->ebuckets[0];
-            GrpGeom g{};
-            const uint32_t threads = bucket_threads(c, eb);
-            if (grp_geometry(prm->K, prm->W, eb.G, kMClasses[eb.mclass], threads / 64u, true, eb.logc, eb.layout, &g)) {
-                const uint32_t need = (uint32_t)update_lds_bytes(prm->K, prm->W);
-                const uint32_t s1_bytes = (prm->W * (Y + 1u) * 4u + 15u) & ~15u;
-                // mixed rows: behind the staged single-column table, inside the count tables; uniform rows: the count table
-                const uint32_t off = (eb.layout & 8u) ? g.off_s1 + s1_bytes : g.off_ng;
-                const uint32_t end = (eb.layout & 8u) ? g.off_wave : g.off_n1;
-                if (off + need <= end) {
-                    em->fusable = true;
-                    em->fuse_upd_off = off;
-                    if ((rc = em->mem.alloc(&em->d_s_block, (size_t)eb.blocks * prm->W * (Y + 1u)))) return rc;
-                }
-            }
-        }
+}
+
+// Stage 4, fused updates (update_kernel.h): inside iterate() / optimize() the model update of pass p runs in the block
+// prologue of pass p+1's FIRST launch -- a grouped kernel whose count tables leave room for the update's scratch.  Decides
+// which launch that is, moves it to the front and allocates every block's copy of the odds table.
+int plan_fused_update(bamm_em* em) {
+    const uint32_t K = em->prm.K, W = em->prm.W, Y = em->Y;
+    if (em->sliced || !em->ctx->use_fused_update || !update_fits_lds(K, W) || K > 2u) return BAMM_OK;
+    size_t best = em->ebuckets.size();
+    for (size_t i = 0; i < em->ebuckets.size(); i++)
+        if (em->ebuckets[i].grouped && kMClasses[em->ebuckets[i].mclass] <= BAMM_FUSE_MAX_M &&   // the classes built with the fused prologue
+            (best == em->ebuckets.size() || em->ebuckets[i].count > em->ebuckets[best].count)) best = i;
+    if (best == em->ebuckets.size()) return BAMM_OK;
+    std::swap(em->ebuckets[0], em->ebuckets[best]);
+    const EmBucket& eb = em->ebuckets[0];
+    GrpGeom g{};
+    if (!grp_geometry(K, W, eb.G, kMClasses[eb.mclass], bucket_threads(em->ctx, eb) / 64u, true, eb.logc, eb.layout, &g)) return BAMM_OK;
+    const uint32_t need = (uint32_t)update_lds_bytes(K, W);
+    const uint32_t s1_bytes = (W * (Y + 1u) * 4u + 15u) & ~15u;
+    // mixed rows: behind the staged single-column table, inside the count tables; uniform rows: the count table
+    const uint32_t off = (eb.layout & 8u) ? g.off_s1 + s1_bytes : g.off_ng;
+    const uint32_t end = (eb.layout & 8u) ? g.off_wave : g.off_n1;
+    if (off + need > end) return BAMM_OK;
+    em->fusable = true;
+    em->fuse_upd_off = off;
+    return em->mem.alloc(&em->d_s_block, (size_t)eb.blocks * W * (Y + 1u));
+}
+
+// Stage 5, the sliced path with k_em_seq as its E pass: compacted lists between the E pass and the M slices, and the
+// choice per pass between them and dense r.  Allocates the lists and the two counters; decides the threshold.
+int plan_lists(bamm_em* em, const uint8_t* seq_mask) {
+    const bamm_ctx* c = em->ctx;
+    bamm_seqs* seqs = em->seqs;
+    hipStream_t st = c->stream;
+    if (!em->sliced || !em->e_fused || !c->use_e_list) return BAMM_OK;
+    int rc;
+    if ((rc = em->mem.scratch(&em->d_list_r, (size_t)seqs->total_len)) || (rc = em->mem.scratch(&em->d_list_p, (size_t)seqs->total_len)) ||
+        (rc = em->mem.alloc(&em->d_list_n, (size_t)seqs->n))) return rc;
+    if (hipMemsetAsync(em->d_list_n, 0, (seqs->n ? seqs->n : 1) * sizeof(uint32_t), st) != hipSuccess) { set_error("hipMemsetAsync failed"); return BAMM_ERR_HIP; }
+    // lists or dense r, per pass: the first pass of a handle takes the dense flavour (nothing is known yet: the
+    // counter starts saturated), later ones lists once fewer than list_threshold_pct of the windows are non-zero
+    if ((rc = em->mem.alloc(&em->d_nnz, 2))) return rc;
+    const unsigned long long start[2] = {~0ull, 0ull};
+    if (hipMemcpyAsync(em->d_nnz, start, sizeof start, hipMemcpyHostToDevice, st) != hipSuccess) { set_error("hipMemcpyAsync failed"); return BAMM_ERR_HIP; }
+    unsigned long long windows = 0;
+    for (uint64_t n = 0; n < seqs->n; n++) windows += seqs->h_len[n] - em->prm.W + 1u;
+    if (seq_mask && seqs->n) windows = (unsigned long long)((double)windows * (double)em->n_active / (double)seqs->n);
+    em->nnz_limit = windows / 100u * c->list_threshold_pct;
+    em->adaptive_lists = c->use_adaptive_lists;
+    return BAMM_OK;
+}
+
+}  // namespace
+
+int plan_launches(bamm_em* em, bool global_tables, const uint8_t* seq_mask, Primers& primers) {
+    const bamm_em_params* prm = &em->prm;
+    Planning pl{em, primers};
+    int rc = BAMM_OK;
+    const bool want_grouped = !em->sliced && prm->K <= 3u && em->ctx->use_grouped;
+    // A shard of a sharded set plans its kernels as the whole set would: which rows a sequence is multiplied through
+    // (mixed or uniform) decides the last bit of its responsibilities, so the choice follows the GLOBAL size the caller
+    // names (n_seqs_bound / n_seqs_global; this shard's own count when it names neither) and nothing about the shard:
+    // every length class of a set of `plan_n` sequences is planned as a launch of that many (a class that holds a small
+    // part of a large set pays the larger tables' few microseconds per launch; an estimate of the class's global share
+    // from this shard's own mix of lengths could differ between ranks next to the threshold).  The other input of the
+    // plan, whether most sequences of a class carry exceptions, is the shard's own: a property of the data that holds
+    // for every shard alike on double-stranded sets (each sequence has its strand junction) and on clean single-stranded ones.
+    const uint64_t plan_n = std::max<uint64_t>(std::max<uint64_t>(prm->n_seqs_bound, prm->n_seqs_global), em->seqs->n);
+    for (auto& b : em->seqs->buckets) {                      // the launches of one pass, in the order of the set's buckets
+        if (b.mclass == kLongClass || global_tables) {       // beyond the length classes / tables beyond LDS
+            EmBucket eb;
+            if ((rc = plan_long_bucket(pl, b, global_tables, &eb))) return rc;
+            em->ebuckets.push_back(eb);
+            pl.prime(eb);
+        } else if ((rc = plan_class_split(pl, b, want_grouped, plan_n, em->ebuckets))) return rc;
     }
-    if (sliced && em->e_fused && c->use_e_list) {
-        if ((rc = em->mem.scratch(&em->d_list_r, (size_t)seqs->total_len)) || (rc = em->mem.scratch(&em->d_list_p, (size_t)seqs->total_len)) ||
-            (rc = em->mem.alloc(&em->d_list_n, (size_t)seqs->n))) return rc;
-        if (hipMemsetAsync(em->d_list_n, 0, (seqs->n ? seqs->n : 1) * sizeof(uint32_t), st) != hipSuccess) { set_error("hipMemsetAsync failed"); return BAMM_ERR_HIP; }
-        // lists or dense r, per pass: the first pass of a handle takes the dense flavour (nothing is known yet: the
-        // counter starts saturated), later ones lists once fewer than list_threshold_pct of the windows are non-zero
-        if ((rc = em->mem.alloc(&em->d_nnz, 2))) return rc;
-        const unsigned long long start[2] = {~0ull, 0ull};
-        if (hipMemcpyAsync(em->d_nnz, start, sizeof start, hipMemcpyHostToDevice, st) != hipSuccess) { set_error("hipMemcpyAsync failed"); return BAMM_ERR_HIP; }
-        unsigned long long windows = 0;
-        for (uint64_t n = 0; n < seqs->n; n++) windows += seqs->h_len[n] - prm->W + 1u;
-        if (seq_mask && seqs->n) windows = (unsigned long long)((double)windows * (double)em->n_active / (double)seqs->n);
-        em->nnz_limit = windows / 100u * c->list_threshold_pct;
-        em->adaptive_lists = c->use_adaptive_lists;
-    }
+    plan_launch_sizes(em);
+    if ((rc = plan_fused_update(em)) || (rc = plan_lists(em, seq_mask))) return rc;
+    // index lists and tile offsets are on the device before the plan is handed out (nothing above reads device memory)
+    if (pl.uploads_pending && hipStreamSynchronize(em->ctx->stream) != hipSuccess) { set_error("stream sync failed"); return BAMM_ERR_HIP; }
     return BAMM_OK;
 }
 
