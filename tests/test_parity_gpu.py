@@ -383,8 +383,12 @@ EXTRA_SHAPES = [
 
 @pytest.mark.parametrize("spec", EXTRA_SHAPES, ids=[d["name"] for d in EXTRA_SHAPES])
 def test_shapes_and_length_buckets(spec, gpu_ctx, orc):
-    """Every kernel instantiation (M = 1..32 positions per lane), odd widths, bg orders above and
-    below the motif order, single-window sequences, mixed-length sets."""
+    """Records across the length classes (up to 128 positions per lane), odd widths, bg orders above and below the motif
+    order, single-window sequences, mixed-length sets -- through the kernels the default planner gives them: all of
+    these shapes have K <= 3, so their records of 65..4096 positions (2..64 per lane) go to the grouped-column kernels
+    (k_em_grp, k_em_mix; csrc/plan.cpp: plan_class_split), and only records of up to 64 or of more than 4096 positions,
+    records with more N exceptions than the virtual rows hold and widths beyond the grouped tables reach k_em_seq.
+    The per-column and sliced kernels in every one of their classes: tests/test_em_classes_gpu.py."""
     c = Case(**spec)
     em, ss, kmer, off, vbg = make_em(gpu_ctx, c, orc, optimizeQ=True)
     Kb = min(c.bg_order, c.K)
