@@ -261,6 +261,12 @@ bool mix_geometry(uint32_t K, uint32_t W, int M, uint32_t waves, bool accum, Grp
 // and a 65th cell that takes the adds of the code "no bin"); the fix lanes add to those and log the other columns' sums -- the
 // kernel and the builder of the lane records agree through this
 constexpr uint32_t kMixBinBytes = 65u * 8u;
+// layout bit 4, mixed rows only: the start-anchored flavour of k_em_mix (mixed_kernel.h) -- same tables and LDS geometry, the
+// slots in another frame: slot 0 of lane 0 is position mix_anchor_frame(B), and M slots per lane serve a sequence when
+// 64 M >= mix_anchor_span(L, W, B).  Set per launch by the planner (plan.cpp), never by grp_plan.
+constexpr uint32_t kMixAnchorBit = 16u;
+inline __host__ __device__ int mix_anchor_frame(uint32_t B) { return 1 - 3 * (4 - (int)B); }
+inline uint32_t mix_anchor_span(uint32_t L, uint32_t W, uint32_t B) { return (L - W + 1u) + 2u + 3u * (4u - B); }
 inline __host__ __device__ uint32_t mix_resident_cols(const GrpGeom& g) { return g.wave_bytes / kMixBinBytes; }
 int launch_em_mix(int mclass, bool accum, bool write_r, const GrpKernelArgs& a, uint32_t blocks, uint32_t threads, hipStream_t st);
 int launch_em_mix1(int mclass, bool accum, bool write_r, const GrpKernelArgs& a, uint32_t blocks, uint32_t threads, hipStream_t st);
@@ -269,7 +275,8 @@ int launch_em_grp(int mclass, bool accum, bool write_r, const GrpKernelArgs& a, 
 // lane_records.hip: the lane records of one mixed-row bucket (sv: its launch slots; T groups, the first B narrow; the
 // accumulating layout keeps bins of the motif's first n1c columns resident) into out[sv.count][64]; num_cus == kPrimeOnly
 // loads the builder's code object and launches nothing
-int launch_mix_records(int mclass, const SeqView& sv, const uint4* xrec, uint32_t W, uint32_t T, uint32_t B, uint32_t n1c, uint2* out,
+// frame: position of lane 0's first slot (0, or mix_anchor_frame(B) for the start-anchored flavour)
+int launch_mix_records(int mclass, const SeqView& sv, const uint4* xrec, uint32_t W, uint32_t T, uint32_t B, uint32_t n1c, int frame, uint2* out,
                        uint32_t num_cus, hipStream_t st);
 
 struct SeedKernelArgs {          // Motif::initFromPWM's pass over the sequences (seed.hip)

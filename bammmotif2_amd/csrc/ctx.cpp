@@ -230,6 +230,7 @@ const TuningKey kTuningKeys[] = {
     {"update_blocks", &bamm_ctx::use_update_blocks},
     {"score_tiles", &bamm_ctx::use_score_tiles},
     {"em_tiles", &bamm_ctx::use_em_tiles},
+    {"mix_anchor", &bamm_ctx::use_mix_anchor},
     {"scratch_poison", &bamm_ctx::scratch_poison},
     {"peer_allreduce", &bamm_ctx::use_peer_allreduce},
     {"peer_timeout_ms", &bamm_ctx::peer_timeout_ms, 1, 600000, 1, "1..600000"},

@@ -581,6 +581,17 @@ int bamm_em_plan_mixed(bamm_em* em, uint64_t* mixed_seqs) {
     return BAMM_OK;
 }
 
+int bamm_em_plan_launch(bamm_em* em, uint32_t index, uint64_t* out) {
+    if (!em || !out || index >= em->ebuckets.size()) { set_error("bamm_em_plan_launch: bad argument"); return BAMM_ERR_ARG; }
+    const EmBucket& b = em->ebuckets[index];
+    const bool mixed = b.grouped && (b.layout & 8u);
+    out[0] = b.count;
+    out[1] = b.mclass == kLongClass ? 0u : (uint64_t)kMClasses[b.mclass];
+    out[2] = mixed ? 1u : 0u;
+    out[3] = mixed && (b.layout & kMixAnchorBit) ? 1u : 0u;
+    return BAMM_OK;
+}
+
 int bamm_em_plan_paths(bamm_em* em, int* sliced, int* e_fused, uint64_t* long_seqs) {
     if (!em) { set_error("null em"); return BAMM_ERR_ARG; }
     uint64_t l = 0;

@@ -71,7 +71,11 @@ bool mix_geometry(uint32_t K, uint32_t W, int M, uint32_t waves, bool accum, Grp
 
 bool grp_geometry(uint32_t K, uint32_t W, uint32_t G, int M, uint32_t waves, bool accum, uint32_t logC, uint32_t layout,
                   GrpGeom* out) {
-    if (layout & 8u) return G == 4u && logC == 0u && mix_geometry(K, W, M, waves, accum, out);
+    if (layout & 8u) {                                       // (the flavour is the launch's, not the geometry's: the bit rides along)
+        if (G != 4u || logC != 0u || !mix_geometry(K, W, M, waves, accum, out)) return false;
+        out->layout |= layout & kMixAnchorBit;
+        return true;
+    }
     if (K > 3u || W == 0u || G < 2u || G > 4u || K + G > 5u || (int)G > M) return false;
     const bool fixg = K == 3u;                               // single-column table in global memory unless it fits, bins in the epilogue
     GrpGeom g{};

@@ -169,6 +169,26 @@ __device__ __forceinline__ void grp_step(float (&U)[M], const float (&f)[M]) {
     for (int m = 0; m < G; m++) U[m] = cy[m];
 }
 
+// One step of the chain with the product stationary (mixed_kernel.h, start-anchored): U[m] *= f of the slot D slots further
+// up.  Which register that is and how many lanes away is known at compile time (slot renaming plus whole-lane hops); the
+// last hop is fused into the multiply, the ones before it are moves.  Where no lane is left to take from -- beyond lane 63:
+// positions whose rows are neutral for every group -- the factor is 1.
+template <int M, int D>
+__device__ __forceinline__ void grp_pull(float (&U)[M], const float (&f)[M]) {
+#pragma unroll
+    for (int m = 0; m < M; m++) {
+        const int hops = (m + D) / M;
+        float v = f[(m + D) % M];
+        if (hops == 0) {
+            U[m] = U[m] * v;
+        } else {
+#pragma unroll
+            for (int h = 1; h < hops; h++) v = wave_shl1_or_one(v);
+            U[m] = mul_wave_shl1(U[m], v);
+        }
+    }
+}
+
 // E-step chain over NQ quads of group slots, straight-line: EVERY slot of a quad is multiplied in
 // (the slots in front of the first real group hold 1.0f), so no branch sits between two steps and
 // the shift by G slots per step is pure register renaming.  A guard per step (T is a run-time

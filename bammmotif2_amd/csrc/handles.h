@@ -67,7 +67,8 @@ struct EmBucket {                // one kernel launch of an EM pass
     const uint32_t* d_idx = nullptr;
     bool grouped = false;        // k_em_grp instead of k_em_seq
     uint32_t G = 0;              // its group size
-    uint32_t layout = 0;         // table layout (grp_geometry)
+    uint32_t layout = 0;         // table layout (grp_geometry); with kMixAnchorBit the launch is start-anchored and mclass is the
+                                 // class it RUNS in, shorter than the class of its sequences' lengths
     const uint4* d_xrec = nullptr;
     const uint2* d_lane_rec = nullptr;   // mixed rows: the bucket's lane records (lane_records.h), owned by the handle
     uint32_t blocks = 0, logc = 0, sparse_cap = 0, sparse_bytes = 0;
@@ -152,6 +153,7 @@ struct bamm_ctx {
     bool use_grouped = true, use_sparse = true, use_e_fused = true, use_e_list = true, use_fused_update = true, use_adaptive_lists = true, use_update_blocks = true;
     bool use_em_tiles = true;           // EM handles take sequences beyond the length classes tile by tile (em_tiles.hip); read at bamm_em_create
     bool use_score_tiles = true;        // the scorer takes sequences beyond the length classes tile by tile (scorer.hip); read at every scoring call
+    bool use_mix_anchor = true;         // mixed rows: sequences that fit a shorter length class start-anchored run there (plan.cpp); read at bamm_em_create
     uint32_t list_threshold_pct = 45;   // sliced path: a pass takes lists when fewer than this share of the windows was non-zero in the pass before
     uint32_t group_size = 0;            // 0 = planner's choice
     int group_layout = -1;              // -1 = planner's choice

@@ -76,41 +76,35 @@ __host__ __device__ inline uint32_t mix_fix_word(uint32_t lane, uint32_t W, uint
     return yfix;
 }
 
-// the record of `lane` for the sequence `cur` was fetched for: M positions per lane, motif width W, T groups of which the
-// first B are narrow (fix-lane roles: lane = row * T + group)
-template <int M>
-__device__ __forceinline__ uint2 mix_lane_record(const RawSeqG<M>& cur, int lane, uint32_t W, uint32_t T, uint32_t B, uint32_t n1c) {
-    static_assert(2 * (M - 1) + 12 <= 31, "bit 31 of the window word is the fix-lane flag");
-    const uint32_t L = __builtin_amdgcn_readfirstlane(cur.L);
-    const uint32_t LW1 = L - W + 1u;
-    const uint32_t p0 = (uint32_t)lane * M;
+// the 32-bit window of a sequence's 2-bit stream (wp: its first word) that ends at position pe; 0 before the sequence.  Words
+// past the sequence's end only feed positions whose rows are overridden; the stream buffer carries 80 words of slack
+// behind the last sequence (bamm_seqs_upload)
+__device__ __forceinline__ uint32_t mix_stream_window(const uint32_t* wp, int pe) {
+    if (pe < 0) return 0u;
+    const uint32_t wi = (uint32_t)pe >> 4;
+    const uint32_t lo = wp[wi], hi = wi ? wp[wi - 1u] : 0u;
+    return __builtin_amdgcn_alignbit(hi, lo, 30u - 2u * ((uint32_t)pe & 15u));
+}
 
-    // ---- one 32-bit stream window per lane (it ends at the lane's last position); sE = the window ending at LW1-1
-    uint32_t X, sE;
-    {
-        constexpr int NSEL = RawSeqG<M>::NSEL;
-        const uint32_t wi0 = p0 >> 4;
-        const uint32_t pE = LW1 - 1u, lpE = pE / (uint32_t)M;
-        const uint32_t pe = p0 + (uint32_t)(M - 1);
-        const uint32_t sel = (pe >> 4) - wi0;
-        uint32_t lo = cur.w[1], hi = cur.w[0];
-#pragma unroll
-        for (int c = 1; c < NSEL; c++) {
-            lo = (sel == (uint32_t)c) ? cur.w[c + 1] : lo;
-            hi = (sel == (uint32_t)c) ? cur.w[c] : hi;
-        }
-        X = __builtin_amdgcn_alignbit(hi, lo, 30u - 2u * (pe & 15u));
-        sE = (uint32_t)__builtin_amdgcn_readlane((int)X, (int)lpE) >> (2u * ((uint32_t)(M - 1) - (pE - lpE * (uint32_t)M)));
-    }
+// the record of `lane` for a sequence of length L with stream words wp and sequence record xr: M slots per lane, slot 0 of
+// lane 0 at position `frame` (0, or mix_anchor_frame(B) for the start-anchored flavour), motif width W, T groups of which
+// the first B are narrow (fix-lane roles: lane = row * T + group)
+template <int M>
+__device__ __forceinline__ uint2 mix_lane_record(const uint32_t* wp, uint32_t L, uint4 xr, int lane, uint32_t W, uint32_t T, uint32_t B, uint32_t n1c,
+                                                 int frame) {
+    static_assert(2 * (M - 1) + 12 <= 31, "bit 31 of the window word is the fix-lane flag");
+    const uint32_t LW1 = L - W + 1u;
+    // ---- one 32-bit stream window per lane (it ends at the position of the lane's last slot); sE = the window ending at LW1-1
+    uint32_t X = mix_stream_window(wp, lane * M + (M - 1) + frame);
+    const uint32_t sE = mix_stream_window(wp, (int)LW1 - 1);
 
     // ---- virtual rows (one index for both tables): B group ends from xlo on next to an exception, the
     // positions LW1 .. LW1+2 whose groups are cut by the edge
-    const uint32_t xw = __builtin_amdgcn_readfirstlane(cur.xr.x);
     const uint32_t lane_b = (uint32_t)lane / T, lane_t = (uint32_t)lane - lane_b * T;     // fix-lane roles: (row, group)
     const uint32_t lane_G = lane_t >= B ? 4u : 3u;
-    const uint32_t xfields = xrec_fields<7>(cur.xr.y, cur.xr.z, cur.xr.w, lane_b + 4u - lane_G);     // the fields of the group's columns
+    const uint32_t xfields = xrec_fields<7>(xr.y, xr.z, xr.w, lane_b + 4u - lane_G);     // the fields of the group's columns
     bool fix;
-    const uint32_t yfix = mix_fix_word((uint32_t)lane, W, T, B, n1c, L, xw, xfields, sE, &fix);
+    const uint32_t yfix = mix_fix_word((uint32_t)lane, W, T, B, n1c, L, xr.x, xfields, sE, &fix);
     X = (X & ~kMixFixBit) | (fix ? kMixFixBit : 0u);
     return make_uint2(X, yfix);
 }

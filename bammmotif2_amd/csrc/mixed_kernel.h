@@ -65,9 +65,19 @@ __device__ __forceinline__ void lds_add_u64_exec_big(uint32_t byte_addr, unsigne
     lds_add_u64_exec<OFF>(byte_addr, v, mask);
 }
 
-template <int M, int A, int NQ, bool ACCUM, bool WRITE_R, int THREADS>
+// ANCH, the start-anchored flavour (layout bit kMixAnchorBit): the same tables, rows, fix lanes and harvest in another frame.
+// Above, a window's product travels up to the slot of its LAST position, so the slots must reach position L - 1 although no
+// row from L - W + 3 on is anything but neutral.  Here the product of window s stays in the slot of its first quad entry's
+// group end (position s + 2 - 3 pad) and the gathered odds come DOWN to it (grp_pull: by 3, 6, 9 slots for the quad's
+// entries, 13 and 17 for the wide groups); the M-step's integers start there and move UP through the group ends (3, 3, 3, 4, 4;
+// integer adds commute, so the first group's go first).  Slot lane * M + m holds position lane * M + m + 1 - 3 pad; M slots per
+// lane reach every row that is not neutral when 64 M >= L - W + 3 + 3 pad, which for 200 bp on both strands (L = 401, W = 20)
+// is 6 per lane instead of 7.  Same factors in the same order: a window's unnormalised product has the same bits in both
+// flavours; Z sums them over another assignment of windows to lanes.
+template <int M, int A, int NQ, bool ACCUM, bool WRITE_R, int THREADS, bool ANCH = false>
 __global__ void __launch_bounds__(THREADS) k_em_mix(GrpKernelArgs ga) {
     static_assert(M >= 4 && 2 * (M - 1) + 12 <= 32, "a wide group within one lane's run, rows out of one stream window");
+    static_assert(!ANCH || NQ == 1, "the start-anchored chain is written for one quad of narrow groups");
     static_assert(A == 1 || A == 2, "wide groups");
     constexpr uint32_t WAVES = THREADS / 64, V = WAVES * kMixBv;
     constexpr uint32_t R5N = 1024u, R5V0 = R5N + 1u, R5T = R5V0 + V;          // neutral row, first virtual row, rows
@@ -253,7 +263,8 @@ __global__ void __launch_bounds__(THREADS) k_em_mix(GrpKernelArgs ga) {
         __builtin_amdgcn_s_setprio(0);                       // decode, fix lanes
         const uint32_t L = __builtin_amdgcn_readfirstlane(cur.L);
         const uint32_t LW1 = L - W + 1u;
-        const uint32_t p0 = (uint32_t)lane * M;
+        // position of the lane's first slot (ANCH: may lie before the sequence -- the wrapped value is beyond every edge, a neutral row)
+        const uint32_t p0 = ANCH ? (uint32_t)lane * M + (uint32_t)mix_anchor_frame(B) : (uint32_t)lane * M;
 
         // ---- the lane's record (lane_records.h): its 32-bit stream window (it ends at the lane's last position) and, for a
         // fix lane, the y of its up to four columns -- 7 bits each (Y = none), in ONE register: it lives until the virtual
@@ -335,17 +346,46 @@ __global__ void __launch_bounds__(THREADS) k_em_mix(GrpKernelArgs ga) {
                 else asm volatile("ds_read_b32 %0, %1" : "=v"(pr[m].x) : "v"(sg6_base + row6[m] * 4u));
 #endif
             }
-            grp_chain<M, 3, NQ>(ra, U);                      // waits with lgkmcnt(0): the reads above have landed as well
-            lds_wait(pr);
-            float w0[M];
+            if constexpr (ANCH) {
+                // the product stays, the odds of the later groups come down to it: ((((x y) z) w) w0) w1 as above
+                f32x4 sv[M];
 #pragma unroll
-            for (int m = 0; m < M; m++) w0[m] = pr[m].x;
-            grp_step<M, 4>(U, w0);
-            if constexpr (A == 2) {
-                float w1[M];
+                for (int m = 0; m < M; m++) sv[m] = lds_read_b128_off<0>(ra[m]);
+                lds_wait(sv);                                // lgkmcnt(0): the wide groups' odds have landed as well
+                lds_wait(pr);
+                float f[M];
 #pragma unroll
-                for (int m = 0; m < M; m++) w1[m] = pr[m].y;
-                grp_step<M, 4>(U, w1);
+                for (int m = 0; m < M; m++) U[m] = sv[m].x;
+#pragma unroll
+                for (int m = 0; m < M; m++) f[m] = sv[m].y;
+                grp_pull<M, 3>(U, f);
+#pragma unroll
+                for (int m = 0; m < M; m++) f[m] = sv[m].z;
+                grp_pull<M, 6>(U, f);
+#pragma unroll
+                for (int m = 0; m < M; m++) f[m] = sv[m].w;
+                grp_pull<M, 9>(U, f);
+#pragma unroll
+                for (int m = 0; m < M; m++) f[m] = pr[m].x;
+                grp_pull<M, 13>(U, f);
+                if constexpr (A == 2) {
+#pragma unroll
+                    for (int m = 0; m < M; m++) f[m] = pr[m].y;
+                    grp_pull<M, 17>(U, f);
+                }
+            } else {
+                grp_chain<M, 3, NQ>(ra, U);                      // waits with lgkmcnt(0): the reads above have landed as well
+                lds_wait(pr);
+                float w0[M];
+#pragma unroll
+                for (int m = 0; m < M; m++) w0[m] = pr[m].x;
+                grp_step<M, 4>(U, w0);
+                if constexpr (A == 2) {
+                    float w1[M];
+#pragma unroll
+                    for (int m = 0; m < M; m++) w1[m] = pr[m].y;
+                    grp_step<M, 4>(U, w1);
+                }
             }
         }
         __builtin_amdgcn_s_setprio(1);                       // normalisation, statistics
@@ -354,10 +394,11 @@ __global__ void __launch_bounds__(THREADS) k_em_mix(GrpKernelArgs ga) {
             last_LW1 = LW1;
             // q/LW1 for the slots that hold a window (it ends at p: p + 1 >= W and p < L), 0 for the others: kept
             // per distinct length, one multiply per slot instead of two compares, a select and a multiply
+            // (ANCH: the slot holds the window that starts at lane * M + m - 1, whatever pad is)
 #pragma unroll
             for (int m = 0; m < M; m++) {
-                const uint32_t p = p0 + m;
-                pos_m[m] = ((p + 1u >= W) && (p < L)) ? pos_i : 0.0f;
+                const uint32_t p = p0 + m, s = (uint32_t)lane * M + m - 1u;
+                pos_m[m] = (ANCH ? s < LW1 : (p + 1u >= W) && (p < L)) ? pos_i : 0.0f;
             }
         }
         float zpart = 0.0f;
@@ -378,10 +419,19 @@ __global__ void __launch_bounds__(THREADS) k_em_mix(GrpKernelArgs ga) {
 
         if (WRITE_R) {                                       // EM::getR layout: r[L-W-i], i = p-W+1
             float* ro = a.r_out + (a.sv.pos_off[seq] - a.r_base);
+            if constexpr (ANCH) {                            // keyed by the window's start; the W - 1 entries behind the last window are 0
 #pragma unroll
-            for (int m = 0; m < M; m++) {
-                const uint32_t p = p0 + m;
-                if (p < L) ro[L - 1u - p] = U[m];
+                for (int m = 0; m < M; m++) {
+                    const uint32_t s = (uint32_t)lane * M + m - 1u;
+                    if (s < LW1) ro[LW1 - 1u - s] = U[m];
+                }
+                if ((uint32_t)lane < W - 1u) ro[LW1 + (uint32_t)lane] = 0.0f;
+            } else {
+#pragma unroll
+                for (int m = 0; m < M; m++) {
+                    const uint32_t p = p0 + m;
+                    if (p < L) ro[L - 1u - p] = U[m];
+                }
             }
         }
 
@@ -400,34 +450,66 @@ __global__ void __launch_bounds__(THREADS) k_em_mix(GrpKernelArgs ga) {
             }
             // F is a ring: logical slot m lives in F[(m + off) mod M]; a step of G moves the G slots that arrive
             // from the next lane in place (one DPP pair each) and their non-zero masks with them
-            static_for<A>([&](auto wc) {
-                constexpr int w = decltype(wc)::value;
-                constexpr int off = (4 * w) % M;
+            if constexpr (ANCH) {
+                // forward: the integers start at the first quad entry's group end and move up to each later group's, the G
+                // slots that arrive from the PREVIOUS lane in place; after d slots logical slot m lives in F[(m - d) mod M]
+                static_for<4 * NQ + A>([&](auto ec) {
+                    constexpr int e = decltype(ec)::value;
+                    constexpr int d = e < 4 * NQ ? 3 * e : 3 * (4 * NQ - 1) + 4 * (e - 4 * NQ + 1);
+                    constexpr int off = (M - d % M) % M;
+                    if constexpr (e > 0) {
+                        constexpr int G = e < 4 * NQ ? 3 : 4;
 #pragma unroll
-                for (int m = 0; m < M; m++)
-                    lds_add_u64_exec_big<(int)(w * R6T * 8u)>(rad6[m], F[(m + off) % M], nz[(m + off) % M]);
+                        for (int c = 0; c < G; c++) {
+                            const int idx = (c + off) % M;
+                            F[idx] = wave_shr1_u64(F[idx]);
+                            nz[idx] <<= 1;
+                        }
+                    }
+                    if constexpr (e < 4 * NQ) {
+                        constexpr int u = 4 * NQ - 1 - e;    // the groups are stored last to first
+                        if ((uint32_t)u < B) {
 #pragma unroll
-                for (int c = 0; c < 4; c++) {
-                    const int idx = (c + off) % M;
-                    F[idx] = wave_shl1_u64(F[idx]);
-                    nz[idx] >>= 1;
-                }
-            });
-            static_for<4 * NQ>([&](auto uc) {
-                constexpr int u = decltype(uc)::value;
-                if ((uint32_t)u < B) {
-                    constexpr int off = (4 * A + 3 * u) % M;
+                            for (int m = 0; m < M; m++)
+                                lds_add_u64_exec_big<(int)(u * R5T * 8u)>(rad5[m], F[(m + off) % M], nz[(m + off) % M]);
+                        }
+                    } else {
+                        constexpr int w = A - 1 - (e - 4 * NQ);
+#pragma unroll
+                        for (int m = 0; m < M; m++)
+                            lds_add_u64_exec_big<(int)(w * R6T * 8u)>(rad6[m], F[(m + off) % M], nz[(m + off) % M]);
+                    }
+                });
+            } else {
+                static_for<A>([&](auto wc) {
+                    constexpr int w = decltype(wc)::value;
+                    constexpr int off = (4 * w) % M;
 #pragma unroll
                     for (int m = 0; m < M; m++)
-                        lds_add_u64_exec_big<(int)(u * R5T * 8u)>(rad5[m], F[(m + off) % M], nz[(m + off) % M]);
+                        lds_add_u64_exec_big<(int)(w * R6T * 8u)>(rad6[m], F[(m + off) % M], nz[(m + off) % M]);
 #pragma unroll
-                    for (int c = 0; c < 3; c++) {
+                    for (int c = 0; c < 4; c++) {
                         const int idx = (c + off) % M;
                         F[idx] = wave_shl1_u64(F[idx]);
                         nz[idx] >>= 1;
                     }
-                }
-            });
+                });
+                static_for<4 * NQ>([&](auto uc) {
+                    constexpr int u = decltype(uc)::value;
+                    if ((uint32_t)u < B) {
+                        constexpr int off = (4 * A + 3 * u) % M;
+#pragma unroll
+                        for (int m = 0; m < M; m++)
+                            lds_add_u64_exec_big<(int)(u * R5T * 8u)>(rad5[m], F[(m + off) % M], nz[(m + off) % M]);
+#pragma unroll
+                        for (int c = 0; c < 3; c++) {
+                            const int idx = (c + off) % M;
+                            F[idx] = wave_shl1_u64(F[idx]);
+                            nz[idx] >>= 1;
+                        }
+                    }
+                });
+            }
             // ---- what the virtual count rows collected (one window per cell) goes to the log
             wave_lds_sync();
             unsigned long long acc = 0ull;
@@ -580,12 +662,18 @@ __global__ void __launch_bounds__(THREADS) k_em_mix(GrpKernelArgs ga) {
     }
 }
 
+template <int M, int A, int NQ, int THREADS, bool ANCH>
+int launch_mix_flavour(bool accum, bool write_r, const GrpKernelArgs& a, uint32_t blocks, hipStream_t st) {
+    const size_t lds = a.g.lds_bytes;
+    if (write_r) return launch_kernel(&k_em_mix<M, A, NQ, false, true, THREADS, ANCH>, blocks, THREADS, lds, st, a);
+    if (accum) return launch_kernel(&k_em_mix<M, A, NQ, true, false, THREADS, ANCH>, blocks, THREADS, lds, st, a);
+    return launch_kernel(&k_em_mix<M, A, NQ, false, false, THREADS, ANCH>, blocks, THREADS, lds, st, a);
+}
+
 template <int M, int A, int NQ, int THREADS>
 int launch_mix_variant(bool accum, bool write_r, const GrpKernelArgs& a, uint32_t blocks, hipStream_t st) {
-    const size_t lds = a.g.lds_bytes;
-    if (write_r) return launch_kernel(&k_em_mix<M, A, NQ, false, true, THREADS>, blocks, THREADS, lds, st, a);
-    if (accum) return launch_kernel(&k_em_mix<M, A, NQ, true, false, THREADS>, blocks, THREADS, lds, st, a);
-    return launch_kernel(&k_em_mix<M, A, NQ, false, false, THREADS>, blocks, THREADS, lds, st, a);
+    return (a.g.layout & kMixAnchorBit) ? launch_mix_flavour<M, A, NQ, THREADS, true>(accum, write_r, a, blocks, st)
+                                        : launch_mix_flavour<M, A, NQ, THREADS, false>(accum, write_r, a, blocks, st);
 }
 
 // the launcher of the translation unit for A wide groups (grouped_mix.hip: A = 2, grouped_mix1.hip: A = 1); arguments

@@ -3,7 +3,10 @@
 // carries the fused update and the sliced path's lists; the launch geometry of EM::mask.  Host code only.
 
 #include <atomic>
+#include <climits>
 #include <cmath>
+#include <functional>
+#include <map>
 
 #include "handles.h"
 
@@ -32,7 +35,7 @@ int prime_bucket(bamm_ctx* c, const bamm_em_params& prm, uint32_t Y, bool sliced
     ga.e = a;
     if (!grp_geometry(prm.K, prm.W, eb.G, kMClasses[eb.mclass], threads / 64u, true, eb.logc, eb.layout, &ga.g)) return BAMM_OK;   // (the launch reports it)
     if (eb.layout & 8u)                                      // mixed rows: the builder of the lane records is the handle's first launch
-        if (int rc = launch_mix_records(eb.mclass, SeqView{}, nullptr, prm.W, ga.g.T, ga.g.mixB, 0u, nullptr, kPrimeOnly, c->stream)) return rc;
+        if (int rc = launch_mix_records(eb.mclass, SeqView{}, nullptr, prm.W, ga.g.T, ga.g.mixB, 0u, 0, nullptr, kPrimeOnly, c->stream)) return rc;
     return launch_em_grp(eb.mclass, what.accum, what.write_r, ga, kPrimeOnly, threads, c->stream);
 }
 
@@ -179,7 +182,7 @@ int plan_class_split(Planning& pl, const Bucket& b, bool want_grouped, uint64_t 
     });
     GrpGeom gg{};
     uint32_t glogc = 0, gG = 0, glayout = 0;
-    std::vector<uint32_t> yes, no;
+    std::vector<uint32_t> no;
     if (want_grouped && grp_supported_class(Mcls, K) &&
         grp_plan(K, W, Mcls, waves, 2 * with_exc.load() > b.count, plan_n * (uint64_t)Mcls >= 40000ull * 7ull, c->group_size, c->group_layout, &gG, &glogc, &glayout) &&
         grp_geometry(K, W, gG, Mcls, waves, true, glogc, glayout, &gg)) {
@@ -200,23 +203,77 @@ int plan_class_split(Planning& pl, const Bucket& b, bool want_grouped, uint64_t 
                 if (!capable(seq_at(i))) all_capable.store(false, std::memory_order_relaxed);
         });
         const bool all = all_capable.load();
-        if (all) { eb.count = b.count; eb.d_idx = b.d_idx; }
-        else {
-            for (uint32_t i = 0; i < b.count; i++) (capable(seq_at(i)) ? yes : no).push_back(seq_at(i));
-            if ((rc = upload_ids(pl, yes, &eb))) return rc;
+        // Mixed rows: a sequence RUNS in the shortest class whose 64 M slots reach all of its rows that are not neutral when
+        // the windows are anchored at their start (mixed_kernel.h, ANCH; "mix_anchor" = 0: never) -- 200 bp on both strands
+        // at W = 20 in class 6 instead of 7 -- if that class is shorter than the bucket's and k_em_mix is built for it; else
+        // in the bucket's class, end-anchored as ever.  The rule reads (L, W) only, so every shard of a set takes the same
+        // kernel for the same sequence.  The bucket itself stays classed by L: the scorer and the other kernels read it.
+        int anch_class[kNumMClasses];                        // per span in units of 64 slots: the class to run in, or the bucket's
+        const bool mixed = (glayout & 8u) != 0u;
+        auto run_class = [&](uint32_t n) {
+            if (!mixed || !c->use_mix_anchor) return b.mclass;
+            const uint32_t need = (mix_anchor_span(seqs->h_len[n], W, gg.mixB) + 63u) / 64u;
+            return need < (uint32_t)kNumMClasses ? anch_class[need] : b.mclass;
+        };
+        if (mixed) {
+            for (int need = 0; need < kNumMClasses; need++) {
+                anch_class[need] = b.mclass;
+                for (int ci = 3; ci <= 8 && ci < b.mclass; ci++) {           // the classes launch_mix has
+                    if (kMClasses[ci] < need) continue;
+                    GrpGeom g2{};
+                    const uint32_t w2 = std::min(default_threads(c, ci), grp_max_threads(kMClasses[ci])) / 64u;
+                    if (mix_geometry(K, W, kMClasses[ci], w2, true, &g2)) anch_class[need] = ci;
+                    break;
+                }
+            }
         }
-        if ((glayout & 8u) && eb.count) {
-            // mixed rows: every lane's stream window and fix-lane codes per launch slot of this bucket, derived once
-            // here instead of in every pass (lane_records.h; 512 bytes per sequence, set-sized: from the scratch pool);
-            // gg is the accumulating layout: its resident columns decide what a fix lane has left to log
-            uint2* rec = nullptr;
-            if ((rc = em->mem.scratch(&rec, (size_t)eb.count * 64u))) return rc;
-            if ((rc = launch_mix_records(eb.mclass, make_view(seqs, em->exc, eb.d_idx, eb.count, nullptr), xr->d_xrec, W,
-                                         gg.T, gg.mixB, mix_resident_cols(gg), rec, (uint32_t)std::max(1, c->num_cus), c->stream))) return rc;
-            eb.d_lane_rec = rec;
+        std::atomic<int> cls_lo{INT_MAX}, cls_hi{-1};
+        host_ranges(b.count, [&](uint64_t i0, uint64_t i1) {
+            int lo = INT_MAX, hi = -1;
+            for (uint64_t i = i0; i < i1; i++) {
+                if (!all && !capable(seq_at(i))) continue;
+                const int rcl = run_class(seq_at(i));
+                lo = std::min(lo, rcl); hi = std::max(hi, rcl);
+            }
+            for (int cur = cls_lo.load(); lo < cur && !cls_lo.compare_exchange_weak(cur, lo);) {}
+            for (int cur = cls_hi.load(); hi > cur && !cls_hi.compare_exchange_weak(cur, hi);) {}
+        });
+        // one launch per class run, the bucket's own first: the whole bucket as it stands when nothing splits it, else index lists
+        std::map<int, std::vector<uint32_t>, std::greater<int>> parts;
+        const bool whole = all && cls_lo.load() == cls_hi.load() && cls_hi.load() >= 0;
+        if (whole) parts[cls_lo.load()];
+        else
+            for (uint32_t i = 0; i < b.count; i++) {
+                if (all || capable(seq_at(i))) parts[run_class(seq_at(i))].push_back(seq_at(i));
+                else no.push_back(seq_at(i));
+            }
+        for (auto& part : parts) {
+            EmBucket pb = eb;
+            pb.mclass = part.first;
+            const int Mrun = kMClasses[pb.mclass];
+            const bool anchored = pb.mclass != b.mclass;
+            if (anchored) pb.layout |= kMixAnchorBit;
+            if (whole) { pb.count = b.count; pb.d_idx = b.d_idx; }
+            else if ((rc = upload_ids(pl, part.second, &pb))) return rc;
+            if (mixed && pb.count) {
+                // mixed rows: every lane's stream window and fix-lane codes per launch slot of this launch, derived once
+                // here instead of in every pass (lane_records.h; 512 bytes per sequence, set-sized: from the scratch pool);
+                // the accumulating layout of the class run: its resident columns decide what a fix lane has left to log
+                GrpGeom gr = gg;
+                if (anchored && !grp_geometry(K, W, gG, Mrun, bucket_threads(c, pb) / 64u, true, glogc, glayout, &gr)) {
+                    set_error("mixed rows: no geometry for the start-anchored class %d", Mrun);
+                    return BAMM_ERR_UNSUPPORTED;
+                }
+                uint2* rec = nullptr;
+                if ((rc = em->mem.scratch(&rec, (size_t)pb.count * 64u))) return rc;
+                if ((rc = launch_mix_records(pb.mclass, make_view(seqs, em->exc, pb.d_idx, pb.count, nullptr), xr->d_xrec, W, gr.T, gr.mixB,
+                                             mix_resident_cols(gr), anchored ? mix_anchor_frame(gr.mixB) : 0, rec,
+                                             (uint32_t)std::max(1, c->num_cus), c->stream))) return rc;
+                pb.d_lane_rec = rec;
+            }
+            pb.work = (double)pb.count * Mrun * 0.6;         // grouped passes cost about 60 % per sequence
+            if (pb.count) out.push_back(pb);
         }
-        eb.work = (double)eb.count * Mcls * 0.6;             // grouped passes cost about 60 % per sequence
-        if (eb.count) out.push_back(eb);
         if (all) return BAMM_OK;
     }
     EmBucket eb;

@@ -547,6 +547,16 @@ class EM:
         check(self.lib.bamm_em_plan_mixed(self.h, C.byref(m)))
         return int(m.value)
 
+    def plan_launches(self):
+        """The launches of one pass, in order: dicts of `count` (sequences), `positions_per_lane` of the class the launch runs
+        in (0: beyond the classes), `mixed` (the mixed-row kernel) and `anchored` (its start-anchored flavour)."""
+        out = []
+        for i in range(self.plan()[2]):
+            v = (C.c_uint64 * 4)()
+            check(self.lib.bamm_em_plan_launch(self.h, i, v))
+            out.append(dict(count=int(v[0]), positions_per_lane=int(v[1]), mixed=bool(v[2]), anchored=bool(v[3])))
+        return out
+
     def plan_paths(self):
         """(sliced, e_fused, long_seqs): the pass runs column slices; its E pass still holds the whole odds table; sequences
         that go window by window (include/bamm_em.h: bamm_em_plan_paths)."""

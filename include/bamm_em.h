@@ -130,7 +130,10 @@ int  bamm_ctx_set_launch(bamm_ctx* ctx, uint32_t blocks, uint32_t threads_per_bl
  *   "group_layout" -1 = planner's choice, 0..3 = table layout of the uniform rows (csrc/grouped.hip:
  *                       grp_geometry), 8 = mixed rows only (csrc/mixed_kernel.h; where they do not apply
  *                       the sequences go one column at a time)
- *   "sparse"       1/0  compacted lists of the non-zero windows in the M-step (default 1)
+ *   "mix_anchor"   1/0  mixed rows: a sequence whose rows fit a shorter length class with the windows anchored at
+ *                       their start runs there (default 1; 0 = every sequence in the class of its length).  The
+ *                       two flavours differ in the last bits of r (the summation order of Z), nowhere else
+ *   "sparse"      1/0  compacted lists of the non-zero windows in the M-step (default 1)
  *   "e_fused"      1/0  sliced path: whole-table E pass when the odds table fits LDS (default 1)
  *   "e_list"       1/0  sliced path: the E pass hands the M slices compacted lists of the non-zero
  *                       windows instead of all responsibilities (default 1)
@@ -376,6 +379,11 @@ int  bamm_em_plan(bamm_em* em, uint64_t* grouped_seqs, uint64_t* percolumn_seqs,
 /* of the grouped ones: sequences that go through the mixed-row flavour (csrc/mixed_kernel.h: K = 2, the motif's
  * last W mod 3 groups of four columns on 6-mer rows)                                              */
 int  bamm_em_plan_mixed(bamm_em* em, uint64_t* mixed_seqs);
+/* launch `index` (0 .. launches-1 of bamm_em_plan) of a pass: out[4] = its sequences, the positions per lane of the length
+ * class it RUNS in (0: beyond the classes), 1 for the mixed-row kernel, 1 for that kernel's start-anchored flavour (the
+ * windows anchored at their start: the class run is then shorter than the class of the sequences' lengths; "mix_anchor"
+ * = 0 in bamm_ctx_set_tuning plans none).  BAMM_ERR_ARG beyond the last launch.                                  */
+int  bamm_em_plan_launch(bamm_em* em, uint32_t index, uint64_t* out);
 /* which of the other paths the handle takes: *sliced = 1 when its tables exceed one CU's LDS and a pass runs column
  * slices (k >= 4 at usual widths); *e_fused = 1 when the E pass of such a handle still holds the whole odds table (r in the
  * reference's layout), 0 when it is sliced as well (r per position slot); *long_seqs = sequences outside the length
