@@ -220,6 +220,12 @@ inline size_t update_lds_bytes(uint32_t K, uint32_t W) {   // n of all orders, A
     return (even(v_size(K, W)) + even((size_t)(K + 1) * W) + even(bg_size(K))) * sizeof(float) + (16 + 4) * sizeof(double);
 }
 inline bool update_fits_lds(uint32_t K, uint32_t W) { return ipow4(K + 1) * W <= 2048u && update_lds_bytes(K, W) <= 60u * 1024u; }
+// the form launch_update runs (bamm_em_plan_update reports it): k_update<true>, k_update<false>, or the band kernels when
+// the handle holds their scratch (UpdateArgs::partial, ticket)
+enum UpdateForm : int { kUpdateLds = 0, kUpdateOneBlock = 1, kUpdateBands = 2 };
+inline UpdateForm update_form(uint32_t K, uint32_t W, bool band_scratch) {
+    return update_fits_lds(K, W) ? kUpdateLds : (band_scratch ? kUpdateBands : kUpdateOneBlock);
+}
 
 struct GrpKernelArgs {
     EmKernelArgs e;

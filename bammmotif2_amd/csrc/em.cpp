@@ -602,6 +602,14 @@ int bamm_em_plan_paths(bamm_em* em, int* sliced, int* e_fused, uint64_t* long_se
     return BAMM_OK;
 }
 
+int bamm_em_plan_update(const bamm_em* em, int* form, int* fusable) {
+    if (!em) { set_error("null em"); return BAMM_ERR_ARG; }
+    // prepare_update hands every update the handle's band scratch, allocated at creation or never
+    if (form) *form = update_form(em->prm.K, em->prm.W, em->d_upd_partial != nullptr && em->d_upd_ticket != nullptr);
+    if (fusable) *fusable = em->fusable ? 1 : 0;
+    return BAMM_OK;
+}
+
 int bamm_em_tile_geometry(uint32_t W, uint32_t* tile_positions, uint32_t* stride) {
     if (!em_tile_geometry(W, tile_positions, stride)) {
         set_error("bamm_em_tile_geometry: W=%u leaves a tile no stride of at least 16 positions", W);

@@ -342,9 +342,10 @@ int launch_make_s(const float* v, const float* vbg, uint32_t K, uint32_t W, uint
 int launch_update(const UpdateArgs& a, hipStream_t st) {
     // n and v of all orders staged in LDS when at most two cells per thread of the top order are in flight
     // (the old v[K] is kept in two registers) and the tables fit the default 64 KiB
-    if (update_fits_lds(a.K, a.W)) {
+    const UpdateForm form = update_form(a.K, a.W, a.partial != nullptr && a.ticket != nullptr);
+    if (form == kUpdateLds) {
         hipLaunchKernelGGL(k_update<true>, dim3(1), dim3(1024), update_lds_bytes(a.K, a.W), st, a);
-    } else if (a.partial != nullptr && a.ticket != nullptr) {
+    } else if (form == kUpdateBands) {
         const size_t cells = ipow4(a.K + 1) * a.W;
         const uint32_t b2 = (uint32_t)std::min<size_t>(kUpdateMaxBlocks, (cells + 255) / 256);
         for (uint32_t k_src = a.K;;) {                       // bands of two orders below their source

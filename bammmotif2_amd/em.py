@@ -564,6 +564,14 @@ class EM:
         check(self.lib.bamm_em_plan_paths(self.h, C.byref(sl), C.byref(ef), C.byref(ln)))
         return bool(sl.value), bool(ef.value), int(ln.value)
 
+    def plan_update(self):
+        """(form, fusable): the form of the handle's update launches -- 0 one block with the tables in LDS, 1 one block on
+        global memory, 2 spread over blocks -- and whether iterate() / optimize() run the update of a pass in the
+        prologue of the next pass's first kernel (include/bamm_em.h: bamm_em_plan_update)."""
+        form, fus = C.c_int(-1), C.c_int(-1)
+        check(self.lib.bamm_em_plan_update(self.h, C.byref(form), C.byref(fus)))
+        return int(form.value), bool(fus.value)
+
     def tile_plan(self) -> dict:
         """Of plan_paths()' long_seqs: `tiled_seqs` go tile by tile (csrc/em_tiles.hip) in `tiles` tiles, `window_seqs`
         window by window (bamm_em_tile_plan); decided at creation from the context's `em_tiles` tuning and the model's shape."""

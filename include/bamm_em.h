@@ -390,6 +390,12 @@ int  bamm_em_plan_launch(bamm_em* em, uint32_t index, uint64_t* out);
  * classes: beyond BAMM_MAX_SEQ_POSITIONS, or every sequence of a model whose tables stay in global memory (orders >= 7) --
  * tile by tile or window by window, bamm_em_tile_plan tells which.  Any pointer may be NULL.                   */
 int  bamm_em_plan_paths(bamm_em* em, int* sliced, int* e_fused, uint64_t* long_seqs);
+/* which form of the model update the handle's update launches run: *form = 0 one block with every order of n and v in
+ * LDS (at most 2048 cells of the top order), 1 one block on global memory ("update_blocks" = 0 in bamm_ctx_set_tuning),
+ * 2 spread over blocks in bands of orders; *fusable = 1 when iterate() / optimize() run the update of a pass in the
+ * prologue of the next pass's first kernel instead ("fused_update" = 0 plans none; a caller-owned reduce buffer ends it).
+ * No device work; either pointer may be NULL.                                                                    */
+int  bamm_em_plan_update(const bamm_em* em, int* form, int* fusable);
 /* The tiles an EM pass cuts a sequence longer than BAMM_MAX_SEQ_POSITIONS into, for motifs of width W: the scorer's
  * rule (bamm_score_tile_geometry) with the EM kernels' own positions per lane.  Pure host arithmetic, no device needed;
  * either pointer may be NULL.  BAMM_ERR_ARG for W = 0 and for a W that leaves no stride of at least 16.              */
