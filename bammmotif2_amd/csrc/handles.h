@@ -172,6 +172,7 @@ struct bamm_ctx {
     std::vector<std::pair<void*, size_t>> scratch_idle;      // blocks waiting for their next owner, oldest first
     size_t scratch_idle_bytes = 0, scratch_cap_bytes = 0;
     uint32_t sites_chunk_positions = 0;                      // bamm_em_sites: dense r kept on the device at a time (0 = default)
+    uint32_t neg_segment_positions = 0;                      // bamm_sample_negatives: positions per segment of a long record, rounded down to 16s (0 = default)
     bool scratch_poison = false;                             // tests: every block is filled with 0xFF when it is handed out
     uint64_t scratch_hits = 0, scratch_misses = 0;
     // Every transfer of 64 KiB or more between the CALLER's memory and the device goes through this pinned area (two chunks,

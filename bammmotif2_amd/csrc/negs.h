@@ -26,7 +26,36 @@ struct NegArgs {
     uint32_t* bad;               // counts the draws the reference leaves undefined (rand() == RAND_MAX at a first base)
 };
 
-int launch_neg_counts(const NegArgs& a, hipStream_t st);
+// Positives beyond BAMM_MAX_SEQ_POSITIONS: their negatives are cut into segments of S positions (a multiple of 16, so that a
+// 2-bit output word belongs to one segment), a lane per segment (negs.hip: k_neg_segments).
+constexpr uint32_t kNegSegment = 4096;                       // S unless the context's "neg_segment_positions" says otherwise
+constexpr uint32_t kNegCountWords = 1024;                     // words of a long positive one wave counts (k_neg_counts_long)
+
+struct NegLongRec {              // one kept negative of a long positive
+    uint64_t draw_start;         // its first draw: draw0[n] + f L
+    uint64_t out_off;            // its first output word: out_word_off[n] + kept rank * words per negative
+    uint32_t L, tab;             // positions; its positive's row of NegLongArgs::bar
+};
+
+struct NegLongArgs {
+    const uint64_t* long_pos;    // [n_long] the long positives' indices in the set, ascending
+    uint64_t n_long;
+    const uint64_t* chunk_off;   // [n_long + 1] first counting chunk (kNegCountWords words) of each
+    uint64_t n_chunks;
+    uint32_t* cnt;               // [n_long][kNegTable] their (k+1)-mer counts (zeroed by the caller)
+    float* bar;                  // [n_long][kNegTable] their bars (k_neg_tables)
+    const NegLongRec* rec; uint64_t n_rec;
+    const uint64_t* seg_off;     // [n_rec + 1] first segment of each kept negative
+    uint64_t n_seg;
+    uint32_t S;
+    unsigned long long* map;     // [n_seg] context -> context over the segment, 16 x 4 bits
+    uint32_t* state;             // [34][n_seg] the generator at the segment's first draw
+    uint8_t* entry;              // [n_seg] the context the segment starts in (k_neg_entry)
+};
+
+int launch_neg_counts(const NegArgs& a, hipStream_t st);      // positives up to BAMM_MAX_SEQ_POSITIONS
 int launch_neg_sample(const NegArgs& a, hipStream_t st);
+int launch_neg_counts_long(const NegArgs& a, const NegLongArgs& la, hipStream_t st);   // the longer ones
+int launch_neg_sample_long(const NegArgs& a, const NegLongArgs& la, hipStream_t st);
 
 }  // namespace bamm

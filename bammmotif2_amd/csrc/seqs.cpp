@@ -364,7 +364,7 @@ int bamm_sample_negatives(bamm_ctx* c, bamm_seqs* pos, uint32_t s_order, uint64_
         set_error("the device sampler is written for -s 2 (SeqGenerator.cpp:112-186); other orders run on the host");
         return BAMM_ERR_UNSUPPORTED;
     }
-    if (pos->max_len > BAMM_MAX_SEQ_POSITIONS || pos->n == 0) { set_error("the device sampler takes non-empty sets of sequences up to %u positions", BAMM_MAX_SEQ_POSITIONS); return BAMM_ERR_UNSUPPORTED; }
+    if (pos->n == 0) { set_error("the device sampler takes non-empty sets"); return BAMM_ERR_UNSUPPORTED; }
     if (!GlibcRandStream::libc_is_this_generator()) {
         set_error("libc's rand() is not the restated glibc generator on this host: the sampler runs on the host, drawing from libc itself");
         return BAMM_ERR_UNSUPPORTED;
@@ -385,7 +385,24 @@ int bamm_sample_negatives(bamm_ctx* c, bamm_seqs* pos, uint32_t s_order, uint64_
     if (hipMemsetAsync(a.total_counts, 0, tot * sizeof(unsigned long long), st) != hipSuccess || hipMemsetAsync(a.bad, 0, sizeof(uint32_t), st) != hipSuccess) {
         set_error("hipMemsetAsync failed"); return BAMM_ERR_HIP;
     }
-    if ((rc = launch_neg_counts(a, st))) return rc;
+    // positives beyond the length classes are counted chunk by chunk and sampled segment by segment (negs.hip)
+    NegLongArgs la{};
+    std::vector<uint64_t> long_pos, chunk_off{0};
+    for (uint64_t i = 0; i < pos->n; i++)
+        if (pos->h_len[i] > BAMM_MAX_SEQ_POSITIONS) {
+            long_pos.push_back(i);
+            chunk_off.push_back(chunk_off.back() + (((uint64_t)pos->h_len[i] + 15) / 16 + kNegCountWords - 1) / kNegCountWords);
+        }
+    la.n_long = long_pos.size(); la.n_chunks = chunk_off.back();
+    la.S = c->neg_segment_positions ? c->neg_segment_positions / 16u * 16u : kNegSegment;
+    if (la.n_long) {
+        uint64_t *d_long = nullptr, *d_chunk = nullptr;
+        if ((rc = tmp.upload(&d_long, long_pos.data(), long_pos.size())) || (rc = tmp.upload(&d_chunk, chunk_off.data(), chunk_off.size())) ||
+            (rc = tmp.alloc(&la.cnt, la.n_long * kNegTable)) || (rc = tmp.alloc(&la.bar, la.n_long * kNegTable))) return rc;
+        la.long_pos = d_long; la.chunk_off = d_chunk;
+        if (hipMemsetAsync(la.cnt, 0, la.n_long * kNegTable * sizeof(uint32_t), st) != hipSuccess) { set_error("hipMemsetAsync failed"); return BAMM_ERR_HIP; }
+    }
+    if ((rc = launch_neg_counts(a, st)) || (rc = launch_neg_counts_long(a, la, st))) return rc;
     std::vector<unsigned long long> cnt(tot);
     if (hipMemcpyAsync(cnt.data(), a.total_counts, tot * sizeof(unsigned long long), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
         set_error("bamm_sample_negatives: the counting pass failed"); return BAMM_ERR_HIP;
@@ -427,6 +444,20 @@ int bamm_sample_negatives(bamm_ctx* c, bamm_seqs* pos, uint32_t s_order, uint64_
         first_kept[i + 1] = first_kept[i] + nk;
     }
     const uint64_t n_neg = first_kept[pos->n], n_words = wo[pos->n];
+    // the long positives' kept negatives and their segments
+    std::vector<NegLongRec> rec;
+    std::vector<uint64_t> seg_off{0};
+    for (uint64_t li = 0; li < la.n_long; li++) {
+        const uint64_t i = long_pos[li], L = pos->h_len[i];
+        uint64_t rank = 0;
+        for (uint64_t f = 0; f < m_fold; f++) {
+            if (!kept(i * m_fold + f)) continue;
+            rec.push_back(NegLongRec{draw0[i] + f * L, wo[i] + rank++ * ((L + 15) / 16), (uint32_t)L, (uint32_t)li});
+            seg_off.push_back(seg_off.back() + (L + la.S - 1) / la.S);
+        }
+    }
+    la.n_rec = rec.size(); la.n_seg = seg_off.back();
+    if (la.n_long > UINT32_MAX) { set_error("bamm_sample_negatives: too many long sequences"); return BAMM_ERR_ARG; }
     GlibcRandStream g;
     g.seed(42u);                                             // SeqGenerator.cpp:35
     std::vector<uint32_t> pw(48 * 31, 0);
@@ -449,7 +480,15 @@ int bamm_sample_negatives(bamm_ctx* c, bamm_seqs* pos, uint32_t s_order, uint64_
     if (e == hipSuccess) e = hipMemcpyAsync(d_pw, pw.data(), pw.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st);
     if (e != hipSuccess) { set_error("bamm_sample_negatives: upload failed: %s", hipGetErrorString(e)); return BAMM_ERR_HIP; }
     a.v = d_v; a.bar = d_bar; a.draw0 = d_draw0; a.out_word_off = d_wo; a.seed_state = d_seed; a.pow2 = d_pw;
-    if ((rc = launch_neg_sample(a, st))) return rc;
+    if (la.n_seg) {
+        NegLongRec* d_rec = nullptr;
+        uint64_t* d_seg = nullptr;
+        if ((rc = tmp.upload(&d_rec, rec.data(), rec.size())) || (rc = tmp.upload(&d_seg, seg_off.data(), seg_off.size())) || (rc = tmp.alloc(&la.map, la.n_seg)) ||
+            (rc = tmp.alloc(&la.state, 34 * la.n_seg)) || (rc = tmp.alloc(&la.entry, la.n_seg))) return rc;
+        la.rec = d_rec; la.seg_off = d_seg;
+    }
+    if (la.n_long < pos->n && (rc = launch_neg_sample(a, st))) return rc;
+    if ((rc = launch_neg_sample_long(a, la, st))) return rc;
     // the negatives as a packed set of their own (single strand, no unknown base: no exceptions)
     bamm_packed* p = (bamm_packed*)calloc(1, sizeof(bamm_packed));
     if (!p) { set_error("out of memory"); return BAMM_ERR_ARG; }
@@ -486,6 +525,12 @@ int bamm_sample_negatives(bamm_ctx* c, bamm_seqs* pos, uint32_t s_order, uint64_
     p->total_len = total; p->max_len = mx; p->min_len = n_neg ? mn : 0;
     *packed_out = p;
     if (seqs_out && (rc = bamm_seqs_upload(c, p, 0, n_neg, seqs_out))) { bamm_packed_free(p); *packed_out = nullptr; return rc; }
+    return BAMM_OK;
+}
+
+int bamm_neg_segment_geometry(uint32_t* segment_positions) {
+    if (!segment_positions) { set_error("bamm_neg_segment_geometry: null output"); return BAMM_ERR_ARG; }
+    *segment_positions = kNegSegment;
     return BAMM_OK;
 }
 

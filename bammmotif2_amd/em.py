@@ -654,6 +654,14 @@ def em_tile_geometry(W: int):
     return tp.value, stride.value
 
 
+def neg_segment_geometry() -> int:
+    """Positions per segment of a negative beyond 8192 positions in sample_negatives (bamm_neg_segment_geometry: a pure
+    function, no device needed); a multiple of 16."""
+    s = C.c_uint32()
+    check(abi.load().bamm_neg_segment_geometry(C.byref(s)))
+    return s.value
+
+
 def score_plan(ctx: Context, seqs: SeqSet, K: int, W: int) -> dict:
     """Which scorer the sequences of `seqs` take under the context's tuning (bamm_score_plan): `wave_seqs` in one wavefront's
     registers, `tiled_seqs` cut into `tiles` tiles, `window_seqs` window by window."""

@@ -156,6 +156,9 @@ int  bamm_ctx_set_launch(bamm_ctx* ctx, uint32_t blocks, uint32_t threads_per_bl
  *   "scratch_poison" 1/0 tests: fill every such block with 0xFF bytes when it is handed out (default 0)
  *   "sites_chunk_positions" n  bamm_em_sites: positions of dense r the call keeps on the device at a time (whole
  *                       sequences; 0 = the default, 2^27 positions = 512 MiB); read at the call, not at handle creation
+ *   "neg_segment_positions" n  bamm_sample_negatives: positions per segment of a negative longer than
+ *                       BAMM_MAX_SEQ_POSITIONS (16..2^20, rounded down to a multiple of 16; 0 = the default,
+ *                       bamm_neg_segment_geometry); the same negatives whatever the cut; for measurements
  * There are no environment variables that change what the library computes or launches.          */
 int  bamm_ctx_set_tuning(bamm_ctx* ctx, const char* key, int value);
 /* Device blocks the library has handed to an owner (a sequence set, a handle, a call's temporaries) and not yet taken
@@ -549,11 +552,17 @@ int  bamm_seqs_bg_model(bamm_ctx* ctx, bamm_seqs* seqs, uint32_t K, const float*
  * reference's negatives, base for base.  keep_stride > 1: only the negatives 0, stride, 2 stride, ... (with idx + stride <=
  * total) are generated and returned, which is all --FDR scores (FDR.cpp:58-60); the others still own their draws.
  * generic != 0: --genericNeg (the set's own conditionals for every positive).  *packed_out: the negatives as a packed set
- * (single strand, no exceptions; bamm_packed_free), *seqs_out (may be NULL): resident.  BAMM_ERR_UNSUPPORTED (the
- * caller samples on the host instead): s_order != 2, sequences beyond BAMM_MAX_SEQ_POSITIONS, a libc whose rand() is
- * not glibc's generator.                                                                                          */
+ * (single strand, no exceptions; bamm_packed_free), *seqs_out (may be NULL): resident.  Any length: a negative of a
+ * positive beyond BAMM_MAX_SEQ_POSITIONS is cut into segments (bamm_neg_segment_geometry), a lane per segment: from its
+ * third position on a base is a function of the two bases before it and of its own draw, so a segment is a map over 16
+ * contexts, and the maps compose exactly.  BAMM_ERR_UNSUPPORTED (the caller samples on the host instead): s_order != 2,
+ * an empty set, a libc whose rand() is not glibc's generator.                                                     */
 int  bamm_sample_negatives(bamm_ctx* ctx, bamm_seqs* positives, uint32_t s_order, uint64_t m_fold, int generic,
                            uint64_t keep_stride, bamm_packed** packed_out, bamm_seqs** seqs_out);
+/* Positions per segment of a long negative (a multiple of 16: a 2-bit word belongs to one segment), as
+ * bamm_sample_negatives cuts it unless "neg_segment_positions" is set.  Pure, no device needed: tests use it to place
+ * sequence lengths on the cuts.                                                                                   */
+int  bamm_neg_segment_geometry(uint32_t* segment_positions);
 
 /* ------------------------------------------------------------------ small host helpers -- */
 /* BackgroundModel ctor + calculateV (BackgroundModel.cpp:3-46, :441-473): interpolated
