@@ -28,6 +28,7 @@ def build(ctx, N, L0, W, K, ss=False, n_frac=0.0, ragged=0, seed=5, fused=True, 
         em = bm.EM(ctx, seqs, K, W, vbg, A, v0, 0.3, mask=mask, **kw)
     finally:
         ctx.set_tuning(fused_update=1)
+    assert em.plan_update() == (0, fused)                    # a shape the planner declines to fuse compares nothing
     return em, seqs
 
 
@@ -40,7 +41,7 @@ def same_trace(a, b):
 SHAPES = [
     dict(N=3000, L0=200, W=20, K=2),                       # both strands: mixed rows when large enough, else uniform rows
     dict(N=2000, L0=120, W=12, K=2, n_frac=0.01, ragged=30),   # N exceptions: a per-column launch follows the fused one
-    dict(N=1500, L0=90, W=9, K=1, ss=True),
+    dict(N=1500, L0=130, W=9, K=1, ss=True),               # 3 positions per lane: the shortest class K = 1 has a grouped kernel for (G = 3)
     dict(N=1200, L0=150, W=15, K=0, ragged=20),
     dict(N=45000, L0=200, W=20, K=2),                      # enough work for the mixed-row kernel
 ]
