@@ -15,7 +15,7 @@ import subprocess
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libbamm_em.so")
-SOURCES = ["model.hip", "kernels.hip", "grouped.hip", "grouped_long.hip", "grouped_xl.hip", "grouped_mix.hip", "grouped_mix1.hip", "lane_records.hip", "mask.hip", "seed.hip", "long_seq.hip", "scorer.hip", "em_tiles.hip", "prep.hip", "negs.hip", "occ.hip", "sites.hip", "fdr.hip", "ctx.cpp", "seqs.cpp", "plan.cpp", "em_pass.cpp", "em.cpp",
+SOURCES = ["model.hip", "kernels.hip", "grouped.hip", "grouped_long.hip", "grouped_xl.hip", "grouped_mix.hip", "grouped_mix1.hip", "lane_records.hip", "mask.hip", "seed.hip", "long_seq.hip", "scorer.hip", "em_tiles.hip", "prep.hip", "negs.hip", "occ.hip", "sites.hip", "fdr.hip", "ctx.cpp", "seqs.cpp", "negs.cpp", "plan.cpp", "em_pass.cpp", "em.cpp",
            "score.cpp", "occurrences.cpp", "sites.cpp", "fdr_stats.cpp", "comm.cpp", "pack.cpp"]
 HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "device_utils.h"), os.path.join(CSRC, "mclass.h"), os.path.join(CSRC, "tiles.h"), os.path.join(CSRC, "grouped_kernel.h"), os.path.join(CSRC, "mixed_kernel.h"), os.path.join(CSRC, "lane_records.h"), os.path.join(CSRC, "update_kernel.h"), os.path.join(CSRC, "phase_clock.h"),
            os.path.join(HERE, "..", "include", "bamm_em.h")]
@@ -134,7 +134,8 @@ EXTRA_DEPS = {"prep.hip": [os.path.join(CSRC, "prep.h")], "negs.hip": [os.path.j
               "occurrences.cpp": _HANDLES + [os.path.join(CSRC, "occ_pvalue.h")],
               "fdr.hip": [os.path.join(CSRC, "fdr_rows.h"), os.path.join(CSRC, "sort_key.h")], "occ.hip": [os.path.join(CSRC, "sort_key.h")],
               "fdr_stats.cpp": _HANDLES + [os.path.join(CSRC, "fdr_rows.h")],
-              "seqs.cpp": _HANDLES + [os.path.join(CSRC, "negs.h"), os.path.join(CSRC, "glibc_rand.h")],
+              "seqs.cpp": _HANDLES,
+              "negs.cpp": _HANDLES + [os.path.join(CSRC, f) for f in ("negs.h", "glibc_rand.h", "neg_layout.h", "packed_set.h")],
               "pack.cpp": [os.path.join(CSRC, "glibc_rand.h"), os.path.join(CSRC, "prep.h")]}
 FLAGS_STAMP = os.path.join(OBJDIR, "flags.txt")
 
@@ -228,12 +229,13 @@ HOST_SHARED = ["io.cpp", "fdr.cpp", "slot_plan.cpp"]
 HOST_SOURCES = HOST_SHARED + ["hooks.cpp"]
 CLI_SOURCES = ["main.cpp", "options.cpp", "context.cpp", "negatives.cpp", "em_run.cpp", "score.cpp", "folds.cpp"] + HOST_SHARED
 HOST_HEADERS = ["bamm_host.h", "host_util.h", "row_text.h", "neg_sampler.h", "slot_plan.h", "options.h", "driver.h"]
+HOST_CSRC_HEADERS = ["occ_pvalue.h", "fdr_rows.h", "glibc_rand.h", "neg_layout.h"]   # csrc headers the host units include
 
 
 def build_host(force: bool = False, verbose: bool = False):
     """C++17 host code: libbamm_host.so (test hooks) and the `BaMMmotif` drop-in CLI."""
     build_library(force=False, verbose=verbose)
-    deps = [os.path.join(HOST, f) for f in sorted(set(HOST_SOURCES + CLI_SOURCES)) + HOST_HEADERS] + [os.path.join(CSRC, "occ_pvalue.h"), os.path.join(CSRC, "fdr_rows.h"), LIB]
+    deps = [os.path.join(HOST, f) for f in sorted(set(HOST_SOURCES + CLI_SOURCES)) + HOST_HEADERS] + [os.path.join(CSRC, f) for f in HOST_CSRC_HEADERS] + [LIB]
     outs = [HOST_LIB, CLI]
     if not force and all(os.path.exists(o) for o in outs) and \
             min(os.path.getmtime(o) for o in outs) >= max(os.path.getmtime(d) for d in deps):

@@ -1,5 +1,5 @@
 // The handles behind the C ABI (include/bamm_em.h) and the helpers their host units share: ctx.cpp (contexts, staging,
-// scratch pool), seqs.cpp (resident sequence sets), plan.cpp (launch plan of an EM handle), em_pass.cpp (one pass, one
+// scratch pool), seqs.cpp (resident sequence sets), negs.cpp (the negative sampler), plan.cpp (launch plan of an EM handle), em_pass.cpp (one pass, one
 // update, the all-reduce), em.cpp (the EM entry points), score.cpp (the scorer), occurrences.cpp (window p-values) and sites.cpp (windows with r >= cut-off).  Host units only -- no kernel includes it.
 //
 // Who owns what: every device block of a sequence set or an EM handle belongs to the handle's one DevBlocks member

@@ -1,0 +1,64 @@
+// A bamm_packed (include/bamm_em.h) on the host: who owns it until the caller does, the one place its seven arrays are
+// allocated, and the one place lengths become its header.  negs.cpp builds the sampled negatives' set through these; pack.cpp
+// and bamm_seqs_from_codes still allocate by hand (see HISTORY.md).  No HIP here: it compiles with plain g++.
+#pragma once
+#include <cstdlib>
+#include <memory>
+
+#include "../../include/bamm_em.h"
+
+namespace bamm {
+
+void set_error(const char* fmt, ...);                         // pack.cpp
+
+// owns a set until release() hands it to the caller of the C ABI (who calls bamm_packed_free)
+struct PackedFree { void operator()(bamm_packed* p) const { bamm_packed_free(p); } };
+using PackedPtr = std::unique_ptr<bamm_packed, PackedFree>;
+
+// A set of these counts with all seven arrays, zeroed.  Every array has at least one element: the Python views map
+// max(count, 1) elements of each.
+inline int packed_alloc(uint64_t n_seqs, uint64_t n_words, uint64_t n_exc, PackedPtr* out) {
+    PackedPtr p((bamm_packed*)calloc(1, sizeof(bamm_packed)));
+    if (p) {
+        p->n_seqs = n_seqs; p->n_words = n_words; p->n_exc = n_exc;
+        const size_t ne = n_exc ? n_exc : 1;
+        p->words = (uint32_t*)calloc(n_words ? n_words : 1, sizeof(uint32_t));
+        p->word_off = (uint64_t*)calloc(n_seqs + 1, sizeof(uint64_t));
+        p->len = (uint32_t*)calloc(n_seqs ? n_seqs : 1, sizeof(uint32_t));
+        p->exc_off = (uint64_t*)calloc(n_seqs + 1, sizeof(uint64_t));
+        p->exc_pos = (uint32_t*)calloc(ne, sizeof(uint32_t));
+        p->exc_kmer = (uint32_t*)calloc(ne, sizeof(uint32_t));
+        p->exc_clean = (uint32_t*)calloc(ne, sizeof(uint32_t));
+    }
+    if (!p || !p->words || !p->word_off || !p->len || !p->exc_off || !p->exc_pos || !p->exc_kmer || !p->exc_clean) {
+        set_error("out of memory");
+        return BAMM_ERR_ARG;
+    }
+    *out = std::move(p);
+    return BAMM_OK;
+}
+
+// The length rule: 16 positions per 32-bit word, every sequence on a word boundary.  From p->n_seqs lengths (`lens` may
+// be p->len itself) it fills len, word_off, n_words, total_len, max_len and min_len (0 for an empty set).  exc_off is
+// left as it is: all zero as allocated, which is right for a set given by its lengths alone (no exceptions).  On a bare
+// header (len and word_off null) it only counts, which tells packed_alloc's caller the words before anything is allocated.
+template <class L>
+int packed_set_lengths(bamm_packed* p, const L* lens) {
+    const bool store = p->word_off != nullptr;
+    uint64_t n_words = 0, total = 0;
+    uint32_t max_len = 0, min_len = p->n_seqs ? UINT32_MAX : 0;
+    for (uint64_t n = 0; n < p->n_seqs; n++) {
+        const uint64_t len = lens[n];
+        if (len > 0xffffffffull) { set_error("sequence %llu longer than 2^32-1", (unsigned long long)n); return BAMM_ERR_ARG; }
+        if (store) { p->len[n] = (uint32_t)len; p->word_off[n] = n_words; }
+        n_words += (len + 15) / 16;
+        total += len;
+        if (len > max_len) max_len = (uint32_t)len;
+        if (len < min_len) min_len = (uint32_t)len;
+    }
+    if (store) p->word_off[p->n_seqs] = n_words;
+    p->n_words = n_words; p->total_len = total; p->max_len = max_len; p->min_len = min_len;
+    return BAMM_OK;
+}
+
+}  // namespace bamm

@@ -1,12 +1,10 @@
 // Resident sequence sets of the C ABI: the 2-bit stream on the device with its length buckets, the per-order exception
 // lists and the grouped kernel's per-sequence records built from them, packing on the device (bamm_seqs_from_codes), the
-// background counts and the negative sampler.  Host code only.
+// background counts.  The negative sampler's host side is negs.cpp.  Host code only.
 
 #include <cstdlib>
 
-#include "glibc_rand.h"
 #include "handles.h"
-#include "negs.h"
 
 namespace bamm {
 
@@ -350,187 +348,6 @@ int bamm_seqs_bg_model(bamm_ctx* c, bamm_seqs* s, uint32_t K, const float* alpha
         if (e != hipSuccess) { set_error("bamm_seqs_bg_model: %s", hipGetErrorString(e)); return BAMM_ERR_HIP; }
     }
     bg_from_top_counts(top.data(), K, alpha, vbg_out);
-    return BAMM_OK;
-}
-
-// SeqGenerator::sample_bgseqset_by_fold (SeqGenerator.cpp:63-348) on the device: csrc/negs.hip
-int bamm_sample_negatives(bamm_ctx* c, bamm_seqs* pos, uint32_t s_order, uint64_t m_fold, int generic, uint64_t keep_stride,
-                          bamm_packed** packed_out, bamm_seqs** seqs_out) {
-    if (!c || !pos || !packed_out || m_fold == 0) { set_error("bamm_sample_negatives: bad argument"); return BAMM_ERR_ARG; }
-    *packed_out = nullptr;
-    if (seqs_out) *seqs_out = nullptr;
-    if (pos->ctx != c) { set_error("sequence set belongs to another context"); return BAMM_ERR_ARG; }
-    if (s_order != kNegMaxOrder) {
-        set_error("the device sampler is written for -s 2 (SeqGenerator.cpp:112-186); other orders run on the host");
-        return BAMM_ERR_UNSUPPORTED;
-    }
-    if (pos->n == 0) { set_error("the device sampler takes non-empty sets"); return BAMM_ERR_UNSUPPORTED; }
-    if (!GlibcRandStream::libc_is_this_generator()) {
-        set_error("libc's rand() is not the restated glibc generator on this host: the sampler runs on the host, drawing from libc itself");
-        return BAMM_ERR_UNSUPPORTED;
-    }
-    BAMM_HIP(hipSetDevice(c->device));
-    hipStream_t st = c->stream;
-    ExcK* exc = nullptr;
-    int rc = exceptions_for_order(pos, s_order, &exc);
-    if (rc) return rc;
-    DevBlocks tmp(c);
-    NegArgs a{};
-    a.words = pos->d_words; a.word_off = pos->d_word_off; a.len = pos->d_len; a.exc_off = exc->d_off; a.exc = exc->d_exc;
-    a.n = pos->n; a.s = s_order; a.generic = generic; a.m_fold = m_fold; a.keep_stride = keep_stride;
-    for (uint32_t k = 0; k <= kNegMaxOrder; k++) a.A[k] = 20.0f;            // SeqGenerator.cpp:29-32
-    const uint32_t tot = (uint32_t)bg_size(s_order);
-    float *d_v = nullptr, *d_bar = nullptr;
-    if ((rc = tmp.alloc(&a.total_counts, tot)) || (rc = tmp.alloc(&d_v, tot)) || (rc = tmp.alloc(&d_bar, tot)) || (rc = tmp.alloc(&a.bad, 1))) return rc;
-    if (hipMemsetAsync(a.total_counts, 0, tot * sizeof(unsigned long long), st) != hipSuccess || hipMemsetAsync(a.bad, 0, sizeof(uint32_t), st) != hipSuccess) {
-        set_error("hipMemsetAsync failed"); return BAMM_ERR_HIP;
-    }
-    // positives beyond the length classes are counted chunk by chunk and sampled segment by segment (negs.hip)
-    NegLongArgs la{};
-    std::vector<uint64_t> long_pos, chunk_off{0};
-    for (uint64_t i = 0; i < pos->n; i++)
-        if (pos->h_len[i] > BAMM_MAX_SEQ_POSITIONS) {
-            long_pos.push_back(i);
-            chunk_off.push_back(chunk_off.back() + (((uint64_t)pos->h_len[i] + 15) / 16 + kNegCountWords - 1) / kNegCountWords);
-        }
-    la.n_long = long_pos.size(); la.n_chunks = chunk_off.back();
-    la.S = c->neg_segment_positions ? c->neg_segment_positions / 16u * 16u : kNegSegment;
-    if (la.n_long) {
-        uint64_t *d_long = nullptr, *d_chunk = nullptr;
-        if ((rc = tmp.upload(&d_long, long_pos.data(), long_pos.size())) || (rc = tmp.upload(&d_chunk, chunk_off.data(), chunk_off.size())) ||
-            (rc = tmp.alloc(&la.cnt, la.n_long * kNegTable)) || (rc = tmp.alloc(&la.bar, la.n_long * kNegTable))) return rc;
-        la.long_pos = d_long; la.chunk_off = d_chunk;
-        if (hipMemsetAsync(la.cnt, 0, la.n_long * kNegTable * sizeof(uint32_t), st) != hipSuccess) { set_error("hipMemsetAsync failed"); return BAMM_ERR_HIP; }
-    }
-    if ((rc = launch_neg_counts(a, st)) || (rc = launch_neg_counts_long(a, la, st))) return rc;
-    std::vector<unsigned long long> cnt(tot);
-    if (hipMemcpyAsync(cnt.data(), a.total_counts, tot * sizeof(unsigned long long), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
-        set_error("bamm_sample_negatives: the counting pass failed"); return BAMM_ERR_HIP;
-    }
-    // the set's conditionals and their bars from the totals (SeqGenerator.cpp:86-110, the float order of host/fdr.cpp)
-    std::vector<float> v(tot, 0.f), bar(tot, 0.f);
-    {
-        auto off = [](uint32_t k) { return (uint32_t)bg_offset(k); };
-        unsigned long long norm = 0;
-        for (uint32_t y = 0; y < 4; y++) norm += cnt[y];
-        float sum = 0.0f;
-        for (uint32_t y = 0; y < 4; y++) {
-            v[y] = ((float)cnt[y] + a.A[0] * 0.25f) / ((float)norm + a.A[0]);
-            sum += v[y];
-            bar[y] = sum;
-        }
-        for (uint32_t k = 1; k <= s_order; k++) {
-            sum = 0.f;
-            for (uint32_t y = 0; y < (uint32_t)ipow4(k + 1); y++) {
-                const uint32_t yk = y / 4, y2 = y % (uint32_t)ipow4(k);
-                v[off(k) + y] = ((float)cnt[off(k) + y] + a.A[k] * v[off(k - 1) + y2]) / ((float)cnt[off(k - 1) + yk] + a.A[k]);
-                if (y % 4 == 0) sum = 0.f;
-                sum += v[off(k) + y];
-                bar[off(k) + y] = sum;
-            }
-        }
-    }
-    // where every positive's draws start, where its kept negatives go; the generator's seed state and the powers t^(2^b)
-    const uint64_t total_neg = pos->n * m_fold;
-    auto kept = [&](uint64_t idx) { return keep_stride <= 1 || (idx % keep_stride == 0 && idx + keep_stride <= total_neg); };
-    std::vector<uint64_t> draw0(pos->n + 1, 0), wo(pos->n + 1, 0), first_kept(pos->n + 1, 0);
-    for (uint64_t i = 0; i < pos->n; i++) {
-        const uint64_t L = pos->h_len[i];
-        uint64_t nk = 0;
-        if (keep_stride <= 1) nk = m_fold;
-        else for (uint64_t f = 0; f < m_fold; f++) nk += kept(i * m_fold + f);
-        draw0[i + 1] = draw0[i] + L * m_fold;
-        wo[i + 1] = wo[i] + nk * ((L + 15) / 16);
-        first_kept[i + 1] = first_kept[i] + nk;
-    }
-    const uint64_t n_neg = first_kept[pos->n], n_words = wo[pos->n];
-    // the long positives' kept negatives and their segments
-    std::vector<NegLongRec> rec;
-    std::vector<uint64_t> seg_off{0};
-    for (uint64_t li = 0; li < la.n_long; li++) {
-        const uint64_t i = long_pos[li], L = pos->h_len[i];
-        uint64_t rank = 0;
-        for (uint64_t f = 0; f < m_fold; f++) {
-            if (!kept(i * m_fold + f)) continue;
-            rec.push_back(NegLongRec{draw0[i] + f * L, wo[i] + rank++ * ((L + 15) / 16), (uint32_t)L, (uint32_t)li});
-            seg_off.push_back(seg_off.back() + (L + la.S - 1) / la.S);
-        }
-    }
-    la.n_rec = rec.size(); la.n_seg = seg_off.back();
-    if (la.n_long > UINT32_MAX) { set_error("bamm_sample_negatives: too many long sequences"); return BAMM_ERR_ARG; }
-    GlibcRandStream g;
-    g.seed(42u);                                             // SeqGenerator.cpp:35
-    std::vector<uint32_t> pw(48 * 31, 0);
-    {
-        uint32_t base[31] = {0, 1}, tmp[31];
-        for (int b = 0; b < 48; b++) {
-            memcpy(pw.data() + 31 * b, base, sizeof base);
-            GlibcRandStream::poly_mul(base, base, tmp);
-            memcpy(base, tmp, sizeof tmp);
-        }
-    }
-    uint64_t *d_draw0 = nullptr, *d_wo = nullptr;
-    uint32_t *d_seed = nullptr, *d_pw = nullptr;
-    if ((rc = tmp.alloc(&d_draw0, pos->n)) || (rc = tmp.alloc(&d_wo, pos->n)) || (rc = tmp.alloc(&d_seed, 34)) || (rc = tmp.alloc(&d_pw, pw.size())) ||
-        (rc = tmp.alloc(&a.out_words, n_words))) return rc;
-    hipError_t e = hipMemcpyAsync(d_v, v.data(), tot * sizeof(float), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_bar, bar.data(), tot * sizeof(float), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess && (ctx_upload(c, d_draw0, draw0.data(), pos->n * sizeof(uint64_t)) || ctx_upload(c, d_wo, wo.data(), pos->n * sizeof(uint64_t)))) e = hipErrorUnknown;
-    if (e == hipSuccess) e = hipMemcpyAsync(d_seed, g.r, 34 * sizeof(uint32_t), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_pw, pw.data(), pw.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st);
-    if (e != hipSuccess) { set_error("bamm_sample_negatives: upload failed: %s", hipGetErrorString(e)); return BAMM_ERR_HIP; }
-    a.v = d_v; a.bar = d_bar; a.draw0 = d_draw0; a.out_word_off = d_wo; a.seed_state = d_seed; a.pow2 = d_pw;
-    if (la.n_seg) {
-        NegLongRec* d_rec = nullptr;
-        uint64_t* d_seg = nullptr;
-        if ((rc = tmp.upload(&d_rec, rec.data(), rec.size())) || (rc = tmp.upload(&d_seg, seg_off.data(), seg_off.size())) || (rc = tmp.alloc(&la.map, la.n_seg)) ||
-            (rc = tmp.alloc(&la.state, 34 * la.n_seg)) || (rc = tmp.alloc(&la.entry, la.n_seg))) return rc;
-        la.rec = d_rec; la.seg_off = d_seg;
-    }
-    if (la.n_long < pos->n && (rc = launch_neg_sample(a, st))) return rc;
-    if ((rc = launch_neg_sample_long(a, la, st))) return rc;
-    // the negatives as a packed set of their own (single strand, no unknown base: no exceptions)
-    bamm_packed* p = (bamm_packed*)calloc(1, sizeof(bamm_packed));
-    if (!p) { set_error("out of memory"); return BAMM_ERR_ARG; }
-    p->n_seqs = n_neg; p->n_words = n_words;
-    p->words = (uint32_t*)malloc((n_words ? n_words : 1) * sizeof(uint32_t));
-    p->word_off = (uint64_t*)calloc(n_neg + 1, sizeof(uint64_t));
-    p->len = (uint32_t*)calloc(n_neg ? n_neg : 1, sizeof(uint32_t));
-    p->exc_off = (uint64_t*)calloc(n_neg + 1, sizeof(uint64_t));
-    p->exc_pos = (uint32_t*)calloc(1, sizeof(uint32_t));
-    p->exc_kmer = (uint32_t*)calloc(1, sizeof(uint32_t));
-    p->exc_clean = (uint32_t*)calloc(1, sizeof(uint32_t));
-    uint32_t bad = 0;
-    bool ok = p->words && p->word_off && p->len && p->exc_off && p->exc_pos && p->exc_kmer && p->exc_clean;
-    if (ok && n_words) ok = ctx_download(c, p->words, a.out_words, n_words * sizeof(uint32_t)) == BAMM_OK;
-    if (ok) ok = hipMemcpyAsync(&bad, a.bad, sizeof bad, hipMemcpyDeviceToHost, st) == hipSuccess;
-    if (ok) ok = hipStreamSynchronize(st) == hipSuccess;
-    if (!ok) { bamm_packed_free(p); set_error("bamm_sample_negatives: the sampling pass failed"); return BAMM_ERR_HIP; }
-    tmp.free_all();                                          // the sampler's buffers go before the negatives' resident set is made
-    if (bad) {                                               // rand() == RAND_MAX at a first base: the reference leaves that byte unset
-        bamm_packed_free(p);
-        set_error("a first base drew rand() == RAND_MAX, which the reference leaves undefined: sample this set on the host");
-        return BAMM_ERR_UNSUPPORTED;
-    }
-    uint64_t at = 0, total = 0;
-    uint32_t mx = 0, mn = UINT32_MAX;
-    for (uint64_t i = 0; i < pos->n; i++) {
-        const uint32_t L = pos->h_len[i];
-        for (uint64_t k = first_kept[i]; k < first_kept[i + 1]; k++) {
-            p->len[k] = L; p->word_off[k] = at; at += (L + 15) / 16; total += L;
-            mx = std::max(mx, L); mn = std::min(mn, L);
-        }
-    }
-    p->word_off[n_neg] = at;
-    p->total_len = total; p->max_len = mx; p->min_len = n_neg ? mn : 0;
-    *packed_out = p;
-    if (seqs_out && (rc = bamm_seqs_upload(c, p, 0, n_neg, seqs_out))) { bamm_packed_free(p); *packed_out = nullptr; return rc; }
-    return BAMM_OK;
-}
-
-int bamm_neg_segment_geometry(uint32_t* segment_positions) {
-    if (!segment_positions) { set_error("bamm_neg_segment_geometry: null output"); return BAMM_ERR_ARG; }
-    *segment_positions = kNegSegment;
     return BAMM_OK;
 }
 

@@ -58,22 +58,15 @@ int sample_negatives(const uint32_t* y_s, const uint64_t* off, size_t n_seqs, ui
     // sequence's draws start is known up front.  With the restated generator (stream.fast) the stream
     // is cut into contiguous ranges, every range jumps to its first draw (GlibcRandStream::jump) and the ranges
     // are sampled on separate threads -- same draws, same negatives.
-    // keep_stride > 1: only the negatives idx = 0, stride, 2 stride, ... with idx + stride <= total are generated and
-    // returned (the others still consume their draws): --FDR scores nothing else (FDR.cpp:58-60).
-    const size_t total_neg = n_seqs * m_fold;
-    auto kept = [&](size_t idx) { return keep_stride <= 1 || (idx % keep_stride == 0 && idx + keep_stride <= total_neg); };
-    std::vector<uint64_t> d0(n_seqs + 1, 0);                 // first draw of positive i
-    std::vector<uint64_t> c0(n_seqs + 1, 0), k0(n_seqs + 1, 0);   // first output byte / first kept negative of positive i
-    for (size_t i = 0; i < n_seqs; i++) {
-        const uint64_t L = off[i + 1] - off[i];
-        size_t nk = 0;
-        for (size_t f = 0; f < m_fold; f++) nk += kept(i * m_fold + f);
-        d0[i + 1] = d0[i] + L * m_fold;
-        c0[i + 1] = c0[i] + L * nk;
-        k0[i + 1] = k0[i] + nk;
-    }
+    // Which negatives are kept under keep_stride, where each positive's draws start and where its kept negatives go is
+    // csrc/neg_layout.h's, shared with the device sampler.
+    const bamm::NegLayout lay(n_seqs, [&](uint64_t i) { return off[i + 1] - off[i]; }, m_fold, keep_stride);
+    const std::vector<uint64_t>& d0 = lay.draw0;             // first draw of positive i
+    const std::vector<uint64_t>& k0 = lay.first_kept;        // first kept negative of positive i
+    std::vector<uint64_t> c0(n_seqs + 1, 0);                 // first output byte of positive i
+    for (size_t i = 0; i < n_seqs; i++) c0[i + 1] = c0[i] + (off[i + 1] - off[i]) * lay.n_kept(i);
     codes_out.resize((size_t)c0[n_seqs]);                     // every byte is written by the range that owns it
-    off_out.assign((size_t)k0[n_seqs] + 1, 0);
+    off_out.assign((size_t)lay.n_neg() + 1, 0);
     const int threads = host_parallelism();
     const bool parallel = g.stream.fast && threads > 1 && n_seqs >= 256;
     const size_t P = parallel ? (size_t)threads : 1;
@@ -99,7 +92,7 @@ int sample_negatives(const uint32_t* y_s, const uint64_t* off, size_t n_seqs, ui
             if (!generic) w.rescale(y_s + off[i], L);
             size_t nk = 0;
             for (size_t f = 0; f < m_fold; f++) {
-                keep_f[f] = kept(i * m_fold + f) ? 1 : 0;
+                keep_f[f] = lay.kept(i, f) ? 1 : 0;
                 if (keep_f[f]) { off_out[(size_t)k0[i] + nk + 1] = c0[i] + L * (nk + 1); nk++; }
             }
             w.draw_many(L, m_fold, codes_out.data() + c0[i], rnd2, ctx2, keep_stride > 1 ? keep_f.data() : nullptr);

@@ -9,6 +9,7 @@
 #include "bamm_host.h"
 #include "host_util.h"
 #include "../csrc/glibc_rand.h"
+#include "../csrc/neg_layout.h"
 
 namespace bammhost {
 
@@ -40,24 +41,7 @@ struct NegSampler {
         }
         for (auto& pt : part)
             for (size_t c = 0; c < n.size(); c++) n[c] += pt[c];
-        size_t norm = 0;
-        for (size_t y = 0; y < 4; y++) norm += n[y];
-        float sum = 0.0f;
-        for (size_t y = 0; y < 4; y++) {
-            v[y] = ((float)n[y] + A[0] * 0.25f) / ((float)norm + A[0]);
-            sum += v[y];
-            range_bar[y] = sum;
-        }
-        for (uint32_t k = 1; k <= s; k++) {
-            sum = 0.f;
-            for (size_t y = 0; y < ipow4(k + 1); y++) {
-                const size_t yk = y / 4, y2 = y % ipow4(k);
-                v[bgoff(k) + y] = ((float)n[bgoff(k) + y] + A[k] * v[bgoff(k - 1) + y2]) / ((float)n[bgoff(k - 1) + yk] + A[k]);
-                if (y % 4 == 0) sum = 0.f;
-                sum += v[bgoff(k) + y];
-                range_bar[bgoff(k) + y] = sum;
-            }
-        }
+        bamm::neg_set_tables(n.data(), s, A.data(), v.data(), range_bar.data(), [](uint32_t k) { return bgoff(k); });   // shared with the device sampler
     }
 
     void rescale(const uint32_t* km, size_t L) {   // :112-186, written for s = 2

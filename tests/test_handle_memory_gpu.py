@@ -10,7 +10,7 @@ import numpy as np
 import pytest
 
 import bammmotif2_amd as bm
-from bammmotif2_amd import synth
+from bammmotif2_amd import abi, synth
 
 pytestmark = pytest.mark.gpu
 
@@ -205,6 +205,49 @@ def test_one_set_serving_two_orders(ctx, packed):
         assert bm.device_blocks_live() > start               # the set's own arrays and tables
         ss.close()
     _twice(cycle)
+
+
+def _four_records():
+    """Single-strand records of 1, 16, 17 and 8193 bases (one beyond the length classes), one N in the 17-base record."""
+    off = np.concatenate([[0], np.cumsum([1, 16, 17, 8193])]).astype(np.uint64)
+    codes = np.random.RandomState(31).randint(1, 5, size=int(off[-1])).astype(np.uint8)
+    codes[int(off[2]) + 5] = 0
+    return codes, off
+
+
+@pytest.mark.parametrize("resident", [False, True])
+@pytest.mark.parametrize("stride", [0, 2])
+def test_sample_negatives_returns_its_temporaries(stride, resident, ctx):
+    """bamm_sample_negatives (csrc/negs.cpp) with a long positive cut into segments of 16 positions.  The positives are made
+    and closed inside the cycle: their order-2 exception table, built by the first sampling call, is theirs to keep."""
+    codes, off = _four_records()
+    ctx.set_tuning(neg_segment_positions=16)
+    try:
+        def cycle(start):
+            pos = bm.SeqSet(ctx, bm.PackedSeqs.from_codes(codes, off, True, seed=42))
+            before = bm.device_blocks_live()
+            neg, res = bm.sample_negatives(ctx, pos, 2, 2, False, stride, resident=resident)
+            assert neg.n_seqs == (4 if stride else 8)
+            if resident:
+                assert bm.device_blocks_live() > before
+                res.close()
+            pos.close()
+        _twice(cycle)
+    finally:
+        ctx.set_tuning(neg_segment_positions=0)
+
+
+def test_sample_negatives_declines_without_a_block(ctx):
+    """s_order = 1: the library's "unsupported" code (the CLI samples on the host on exactly that), nothing left behind."""
+    codes, off = _four_records()
+    pos = bm.SeqSet(ctx, bm.PackedSeqs.from_codes(codes, off, True, seed=42))
+
+    def cycle(start):
+        with pytest.raises(abi.BammError) as err:
+            bm.sample_negatives(ctx, pos, 1, 2, False, 0)
+        assert err.value.code == abi.ERR_UNSUPPORTED
+    _twice(cycle)
+    pos.close()
 
 
 def test_pooled_blocks_return_to_the_context(ctx, packed):

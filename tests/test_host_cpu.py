@@ -96,6 +96,40 @@ def test_pack_empty_and_tiny(lib):
     pk = bm.PackedSeqs.from_kmers(km, np.array([0, 17], np.uint64))
     assert len(pk.words) == 2 and pk.n_exceptions == 0
     assert np.array_equal(pk.unpack_y(10).astype(np.uint64), km)
+    # records on both sides of the word boundaries, through both host packers: the header is the lengths'
+    lens = np.array([15, 16, 17, 33], np.int64)
+    off = np.concatenate([[0], np.cumsum(lens)]).astype(np.uint64)
+    codes = (np.arange(int(off[-1])) % 4 + 1).astype(np.uint8)
+    km = np.zeros(len(codes), np.uint64)
+    for b, e in zip(off[:-1].astype(int), off[1:].astype(int)):
+        roll = 0
+        for i in range(b, e):
+            roll = ((roll << 2) | (int(codes[i]) - 1)) & (4 ** 11 - 1)
+            km[i] = roll
+    sets = [bm.PackedSeqs.from_kmers(km, off), bm.PackedSeqs.from_codes(codes, off, True),
+            bm.PackedSeqs.from_kmers(np.zeros(0, np.uint64), np.zeros(1, np.uint64)), bm.PackedSeqs.from_codes(np.zeros(0, np.uint8), np.zeros(1, np.uint64), True)]
+    for pk, want in zip(sets, (lens, lens, lens[:0], lens[:0])):
+        a = pk.arrays()
+        assert np.array_equal(a["len"], want)
+        assert np.array_equal(a["word_off"], np.concatenate([[0], np.cumsum(-(-want // 16))]))
+        assert int(pk.c.n_words) == int(a["word_off"][-1]) == len(a["words"])
+        assert a["total_len"] == want.sum() and a["max_len"] == (want.max() if len(want) else 0)
+        assert a["min_len"] == (want.min() if len(want) else 0)  # an empty set: 0
+        assert np.array_equal(a["exc_off"], np.zeros(len(want) + 1))
+
+
+def test_packed_layout_check_under_sanitizers(tmp_path):
+    """tools/packed_layout_check.cpp with csrc/pack.cpp, a program of its own under ASan + UBSan: the packed sets above built
+    and freed, csrc/packed_set.h's allocator and length rule, and csrc/neg_layout.h's kept layout against an enumeration of
+    every negative index.  The sanitizer runtimes are linked statically: the program then runs whatever else the process
+    environment preloads (the shared runtime insists on being first in the library list)."""
+    import subprocess
+    root = os.path.dirname(abi.HERE)
+    exe = str(tmp_path / "packed_layout_check")
+    subprocess.check_call(["g++", "-std=c++17", "-fsanitize=address,undefined", "-static-libasan", "-static-libubsan", "-I/opt/rocm/include", "-D__HIP_PLATFORM_AMD__",
+                           os.path.join(root, "tools", "packed_layout_check.cpp"), os.path.join(abi.HERE, "csrc", "pack.cpp"), "-lpthread", "-o", exe])
+    run = subprocess.run([exe], capture_output=True, text=True)
+    assert run.returncode == 0 and run.stdout == "" and run.stderr == "", run.stderr
 
 
 def test_shard_ranges_partition_and_balance(orc, lib):
