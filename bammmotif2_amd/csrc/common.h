@@ -325,6 +325,19 @@ uint32_t score_tile_threads();
 // k_score_tile over every tile, then the per-sequence maxima into k.zoops / k.z
 int launch_score_tiles(const ScoreTileArgs& a, uint32_t blocks, hipStream_t st);
 
+// ---- log-odds tables beyond the LDS of a CU, a slice of motif columns per launch (scorer.hip) ----
+struct ScoreSlice {
+    float*   partial;            // one float per window, indexed as mops (k.mops itself where the caller wants MOPS scores):
+                                 // the sum of columns 0 .. j - 1 of every window between the launches of a call
+    uint32_t j0, j1;             // this launch adds the columns [j0, j1); j1 == W: the last one, which emits and folds
+};
+// columns per slice and slices for a model of order K and width W (bamm_score_slice_geometry); false when W == 0 or not
+// even one column of the table fits the LDS
+bool score_slice_geometry(uint32_t K, uint32_t W, uint32_t* columns_per_slice, uint32_t* slices);
+// k_score / k_score_tile (+ the reduction behind the last slice) over one slice; a.s is the whole table
+int launch_score_slice(int mclass, const ScoreKernelArgs& a, const ScoreSlice& sl, uint32_t blocks, uint32_t threads, hipStream_t st);
+int launch_score_tiles_slice(const ScoreTileArgs& a, const ScoreSlice& sl, uint32_t blocks, hipStream_t st);
+
 // ---- long sequences through the EM pass, tile by tile (em_tiles.hip) ----
 struct EmTileArgs {
     EmKernelArgs e;              // sv: the long sequences of one bucket; a sequence outside sv.mask is skipped inside the kernels

@@ -229,6 +229,7 @@ const TuningKey kTuningKeys[] = {
     {"adaptive_lists", &bamm_ctx::use_adaptive_lists},
     {"update_blocks", &bamm_ctx::use_update_blocks},
     {"score_tiles", &bamm_ctx::use_score_tiles},
+    {"score_slices", &bamm_ctx::use_score_slices},
     {"em_tiles", &bamm_ctx::use_em_tiles},
     {"mix_anchor", &bamm_ctx::use_mix_anchor},
     {"scratch_poison", &bamm_ctx::scratch_poison},

@@ -153,6 +153,7 @@ struct bamm_ctx {
     bool use_grouped = true, use_sparse = true, use_e_fused = true, use_e_list = true, use_fused_update = true, use_adaptive_lists = true, use_update_blocks = true;
     bool use_em_tiles = true;           // EM handles take sequences beyond the length classes tile by tile (em_tiles.hip); read at bamm_em_create
     bool use_score_tiles = true;        // the scorer takes sequences beyond the length classes tile by tile (scorer.hip); read at every scoring call
+    bool use_score_slices = false;      // ... and a log-odds table beyond the LDS a slice of columns per launch (scorer.hip) instead of window by window; read at every scoring call
     bool use_mix_anchor = true;         // mixed rows: sequences that fit a shorter length class start-anchored run there (plan.cpp); read at bamm_em_create
     uint32_t list_threshold_pct = 45;   // sliced path: a pass takes lists when fewer than this share of the windows was non-zero in the pass before
     uint32_t group_size = 0;            // 0 = planner's choice

@@ -4,7 +4,8 @@
 //   k_long_em     EM::EStep   refinement/EM.cpp:149-196, EM::MStep EM.cpp:231-243, the sum over r of
 //                 EM::optimize_q EM.cpp:509-513, EM::getR's layout EM.cpp:173
 //   k_long_score  ScoreSeqSet::calcLogOdds  seq_scoring/ScoreSeqSet.cpp:41-66 -- the scorer of the log-odds tables
-//                 beyond the LDS (any length then) and of long records under bamm_ctx_set_tuning("score_tiles", 0);
+//                 beyond the LDS (any length then; under "score_slices" = 1 only where not one column of the table
+//                 fits, orders 7..10) and of long records under bamm_ctx_set_tuning("score_tiles", 0);
 //                 while the table fits the LDS, long records are scored tile by tile on the whole GPU instead
 //                 (scorer.hip; score.cpp: score_route)
 //

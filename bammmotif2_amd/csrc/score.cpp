@@ -14,11 +14,22 @@ namespace {
 
 // The scorer a length bucket takes: k_score while a sequence fits one wavefront's registers, beyond that the same chain
 // tile by tile (both in scorer.hip, one chain, the log-odds table in LDS), and the window-by-window scorer (long_seq.hip),
-// which reads the table from global memory, for tables beyond the LDS of a CU (orders >= 6 at usual widths), for widths
-// that leave a tile no stride, and for long sequences under bamm_ctx_set_tuning("score_tiles", 0).
+// which reads the table from global memory, for tables beyond the LDS of a CU (K = 4 from W = 40, K = 5 from W = 10, K = 6
+// from W = 3), for widths that leave a tile no stride, and for long sequences under bamm_ctx_set_tuning("score_tiles", 0).
+// Under bamm_ctx_set_tuning("score_slices", 1) a table beyond the LDS of which at least one column fits (orders up to 6)
+// takes the first two instead, a slice of columns per launch (score_slices: 1 = the table fits whole).
 enum class ScoreRoute { kWave, kTiles, kWindows };
+constexpr size_t kScoreLdsBytes = 160u * 1024u;
+// the slices of columns the LDS kernels take the table in: 1 = whole, 0 = it stays in global memory
+uint32_t score_slices(const bamm_ctx* c, uint32_t K, uint32_t W, uint32_t* columns_per_slice) {
+    uint32_t cps = W, S = 1;
+    if ((size_t)W * (ipow4(K + 1) + 1) * sizeof(float) > kScoreLdsBytes && !(c->use_score_slices && score_slice_geometry(K, W, &cps, &S)))
+        return 0;
+    if (columns_per_slice) *columns_per_slice = cps;
+    return S;
+}
 ScoreRoute score_route(const bamm_ctx* c, const Bucket& bk, uint32_t K, uint32_t W) {
-    if ((size_t)W * (ipow4(K + 1) + 1) * sizeof(float) > 160u * 1024u) return ScoreRoute::kWindows;
+    if (!score_slices(c, K, W, nullptr)) return ScoreRoute::kWindows;
     if (bk.mclass != kLongClass) return ScoreRoute::kWave;
     return c->use_score_tiles && score_tile_geometry(W, nullptr, nullptr) ? ScoreRoute::kTiles : ScoreRoute::kWindows;
 }
@@ -65,6 +76,12 @@ int score_on_device(bamm_ctx* c, bamm_seqs* s, const uint8_t* seq_mask, uint32_t
         (rc = tmp.alloc(&d_zoops, s->n)) || (rc = tmp.alloc(&d_z, s->n)) ||
         (want_mops && (rc = pooled_mops ? tmp.scratch(&d_mops, (size_t)std::max<uint64_t>(1, moff[s->n])) : tmp.alloc(&d_mops, moff[s->n]))) ||
         (seq_mask && (rc = tmp.upload(&d_smask, seq_mask, s->n)))) return rc;
+    // column slices carry a float per window from launch to launch: in the MOPS scores where the caller wants them, else in a
+    // block of the context's scratch pool
+    uint32_t cps = W;
+    const uint32_t slices = score_slices(c, K, W, &cps);
+    float* d_part = d_mops;
+    if (slices > 1 && !d_part && (rc = tmp.scratch(&d_part, (size_t)std::max<uint64_t>(1, moff[s->n])))) return rc;
     if (seq_mask) {                                          // sequences outside the subset report zeros
         hipError_t e = hipMemsetAsync(d_zoops, 0, s->n * sizeof(float), st);
         if (e == hipSuccess) e = hipMemsetAsync(d_z, 0, s->n * sizeof(uint32_t), st);
@@ -77,6 +94,12 @@ int score_on_device(bamm_ctx* c, bamm_seqs* s, const uint8_t* seq_mask, uint32_t
         a.sv = make_view(s, exc, bk.d_idx, bk.count, d_smask);
         a.K = K; a.W = W; a.Y = Y; a.s = d_tab; a.mops = d_mops; a.mops_off = d_moff; a.zoops = d_zoops; a.z = d_z;
         ScoreRoute route = score_route(c, bk, K, W);
+        // the launches of one bucket: a.s whole, or a slice of its columns after the other on the context's stream
+        auto per_slice = [&](auto&& launch) {
+            int r = BAMM_OK;
+            for (uint32_t j0 = 0; j0 < W && !r; j0 += cps) r = launch(ScoreSlice{d_part, j0, std::min(W, j0 + cps)});
+            return r;
+        };
         if (route == ScoreRoute::kTiles) {
             ScoreTileArgs ta{};
             std::vector<uint32_t> toff;
@@ -90,7 +113,9 @@ int score_on_device(bamm_ctx* c, bamm_seqs* s, const uint8_t* seq_mask, uint32_t
                     (rc = tmp.alloc(&ta.tile_idx, tiles))) return rc;
                 ta.k = a; ta.k.sv.mask = nullptr; ta.tile_off = d_toff;
                 const uint32_t waves = score_tile_threads() / 64u;
-                rc = launch_score_tiles(ta, std::min(default_blocks(c, score_tile_threads()), (ta.n_tiles + waves - 1) / waves), st);
+                const uint32_t tblocks = std::min(default_blocks(c, score_tile_threads()), (ta.n_tiles + waves - 1) / waves);
+                rc = slices > 1 ? per_slice([&](const ScoreSlice& sl) { return launch_score_tiles_slice(ta, sl, tblocks, st); })
+                                : launch_score_tiles(ta, tblocks, st);
                 continue;
             }
             route = ScoreRoute::kWindows;                    // (more tiles than a launch indexes: 2^32 of them)
@@ -102,15 +127,34 @@ int score_on_device(bamm_ctx* c, bamm_seqs* s, const uint8_t* seq_mask, uint32_t
         const uint32_t threads = default_threads(c, bk.mclass);
         uint32_t blocks = default_blocks(c, threads);
         blocks = std::max(1u, std::min(blocks, (bk.count + threads / 64u - 1) / (threads / 64u)));
-        rc = launch_score(bk.mclass, a, blocks, threads, st);
+        rc = slices > 1 ? per_slice([&](const ScoreSlice& sl) { return launch_score_slice(bk.mclass, a, sl, blocks, threads, st); })
+                        : launch_score(bk.mclass, a, blocks, threads, st);
     }
     out->mops = d_mops; out->zoops = d_zoops; out->z = d_z;
     return rc;
 }
 
+// the widest slice whose columns fit the LDS, then the fewest slices, then those balanced
+bool score_slice_geometry(uint32_t K, uint32_t W, uint32_t* columns_per_slice, uint32_t* slices) {
+    const uint32_t cmax = (uint32_t)(kScoreLdsBytes / ((ipow4(K + 1) + 1) * sizeof(float)));
+    if (W == 0 || cmax == 0) return false;
+    const uint32_t S = (W + cmax - 1) / cmax;
+    if (columns_per_slice) *columns_per_slice = (W + S - 1) / S;
+    if (slices) *slices = S;
+    return true;
+}
+
 }  // namespace bamm
 
 extern "C" {
+
+int bamm_score_slice_geometry(uint32_t K, uint32_t W, uint32_t* columns_per_slice, uint32_t* slices) {
+    if (K > BAMM_MAX_ORDER || !score_slice_geometry(K, W, columns_per_slice, slices)) {
+        set_error("bamm_score_slice_geometry: K=%u, W=%u: no column of the table fits the LDS", K, W);
+        return BAMM_ERR_ARG;
+    }
+    return BAMM_OK;
+}
 
 int bamm_score_tile_geometry(uint32_t W, uint32_t* tile_positions, uint32_t* stride) {
     if (!score_tile_geometry(W, tile_positions, stride)) {

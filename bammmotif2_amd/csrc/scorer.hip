@@ -3,6 +3,7 @@
 //   k_score              one wavefront per sequence of a length class (up to 8192 positions)
 //   k_score_tile         the same over one tile of one longer sequence
 //   k_score_tile_reduce  that sequence's maximum (ScoreSeqSet.cpp:46-57) over its tiles
+//   k_score_slice, k_score_tile_slice   the first two over a slice of the motif's columns: tables beyond the LDS of a CU
 //
 // A window's score is W additions, left to right, of table entries picked by the k-mers inside the window: it depends on
 // nothing else in the sequence.  Lane l holds M consecutive positions in registers, the table lives in LDS as [W][Y+1]
@@ -50,18 +51,30 @@ static_assert(kTileThreads % 64 == 0 && kTileThreads <= 1024, "whole waves");
 // tried cost one of the two callers: `p < end` is the compare k_score's decode makes too and keeps its 23 classes'
 // registers, but k_score_tile<32, 512> then needs 149 VGPRs instead of 118 and loses a wave per SIMD; `i < n_emit` keeps
 // the tile kernel's and puts more scratch into k_score<56> and <64>.  profiles/scorer_refactor_isa.txt)
+// It is written as its two pieces -- the first column, and n further columns from any state of U -- because the sum can be
+// cut at any column: a slice of columns (k_score_slice, k_score_tile_slice below) puts back the U its predecessor left
+// and goes on with score_chain_columns, so the additions stand here and nowhere else.
 template <int M>
-__device__ __forceinline__ void score_chain(const uint32_t (&y)[M], const float* s_lds, uint32_t W, uint32_t Ys, float (&U)[M]) {
-    const float* sj = s_lds;
+__device__ __forceinline__ void score_chain_open(const uint32_t (&y)[M], const float* s0, float (&U)[M]) {
 #pragma unroll
-    for (int m = 0; m < M; m++) U[m] = sj[y[m]];
-    for (uint32_t j = 1; j < W; j++) {
-        sj += Ys;
+    for (int m = 0; m < M; m++) U[m] = s0[y[m]];
+}
+
+// n further columns; sj: the table row of the first of them
+template <int M>
+__device__ __forceinline__ void score_chain_columns(const uint32_t (&y)[M], const float* sj, uint32_t n, uint32_t Ys, float (&U)[M]) {
+    for (uint32_t j = 0; j < n; j++, sj += Ys) {
         const float carry = wave_shr1(0.0f, U[M - 1]);
 #pragma unroll
         for (int m = M - 1; m >= 1; m--) U[m] = U[m - 1] + sj[y[m]];
         U[0] = carry + sj[y[0]];
     }
+}
+
+template <int M>
+__device__ __forceinline__ void score_chain(const uint32_t (&y)[M], const float* s_lds, uint32_t W, uint32_t Ys, float (&U)[M]) {
+    score_chain_open<M>(y, s_lds, U);
+    score_chain_columns<M>(y, s_lds + Ys, W - 1u, Ys, U);
 }
 
 // the block's copy of the log-odds table
@@ -169,7 +182,159 @@ __global__ void __launch_bounds__(256) k_score_tile_reduce(ScoreTileArgs a) {
     }
 }
 
+// ---- column slices: log-odds tables beyond the LDS of a CU (score_slice_geometry) ----
+// A launch holds the columns [j0, j1) of the table and adds only those.  After column j slot p holds the sum of columns
+// 0..j of window p - j, so the state of the chain after column j1 - 1 is one float per window: the slice writes
+// partial[p + 1 - j1] from slot p, its successor reads partial[p + 1 - j0] back into the same slot -- the registers as the
+// unsliced chain would hold them there -- and goes on adding.  Slots that hold no window of the sequence (of the tile's emit
+// range) restart from 0.0f: their sums are never emitted and never reach a slot that is.  A wave reads and writes the
+// windows of its own sequence or tile only, the launches of a call follow each other on one stream, and the last slice
+// emits and folds the maximum as the unsliced kernels do: the same additions in the same order.
+
+// f(m, i) for every slot m of the lane that holds one of the windows i = 0 .. nwin - 1 after `cols` columns.  The guard in
+// the spelling of the caller's unsliced kernel (see score_chain): BY_END compares the slot with the windows' end as k_score
+// does, otherwise the window with their number as k_score_tile does.
+template <int M, bool BY_END, class F>
+__device__ __forceinline__ void for_each_window(uint32_t p0, uint32_t cols, uint32_t nwin, F&& f) {
+    const uint32_t end = nwin + cols - 1u;
+#pragma unroll
+    for (int m = 0; m < M; m++) {
+        const uint32_t p = p0 + m;
+        if (p + 1u >= cols && (BY_END ? p < end : p + 1u - cols < nwin)) f(m, p + 1u - cols);
+    }
+}
+
+// where slot 0 of the lane finds its window after `cols` columns in an array of the sequence's windows: slot m's is
+// lane_windows(...)[m], one address per lane and a constant beside it (only slots that hold a window are touched)
+__device__ __forceinline__ float* lane_windows(float* windows, uint32_t p0, uint32_t cols) {
+    return windows + ((ptrdiff_t)p0 + 1 - (ptrdiff_t)cols);
+}
+
+// this slice's columns over the windows 0 .. nwin - 1, whose carrier starts at part; false: U holds the windows' scores
+template <int M, bool BY_END>
+__device__ __forceinline__ bool score_chain_slice(const uint32_t (&y)[M], const float* lds, const ScoreSlice& sl, uint32_t W, uint32_t Ys,
+                                                  uint32_t p0, uint32_t nwin, float* part, float (&U)[M]) {
+    if (sl.j0 == 0) {
+        score_chain_open<M>(y, lds, U);
+    } else {
+#pragma unroll
+        for (int m = 0; m < M; m++) U[m] = 0.0f;
+        const float* in = lane_windows(part, p0, sl.j0);
+        for_each_window<M, BY_END>(p0, sl.j0, nwin, [&](int m, uint32_t) { U[m] = in[m]; });
+    }
+    const uint32_t first = sl.j0 == 0 ? 1u : 0u;
+    score_chain_columns<M>(y, lds + first * Ys, sl.j1 - sl.j0 - first, Ys, U);
+    if (sl.j1 == W) return false;
+    float* out = lane_windows(part, p0, sl.j1);
+    for_each_window<M, BY_END>(p0, sl.j1, nwin, [&](int m, uint32_t) { out[m] = U[m]; });
+    return true;
+}
+
+template <int M, int THREADS>
+__global__ void __launch_bounds__(THREADS) k_score_slice(ScoreKernelArgs a, ScoreSlice sl) {
+    extern __shared__ float lds[];
+    const uint32_t W = a.W, Ys = a.Y + 1u;
+    load_table(lds, a.s + (size_t)sl.j0 * Ys, (sl.j1 - sl.j0) * Ys);
+
+    const int lane = threadIdx.x & 63;
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint32_t waves_per_block = blockDim.x >> 6;
+    const uint32_t total_waves = gridDim.x * waves_per_block;
+
+    for (uint32_t t = blockIdx.x * waves_per_block + wave; t < a.sv.count; t += total_waves) {
+        const uint32_t seq = pick_sequence(a.sv, t);
+        if (a.sv.mask && !a.sv.mask[seq]) continue;
+        const uint32_t L = a.sv.len[seq];
+        uint32_t y[M];
+        decode_positions<M>(a.sv, seq, L, a.Y, L, lane, y);
+        const uint32_t p0 = (uint32_t)lane * M, nwin = L - W + 1u;
+        float U[M];
+        if (score_chain_slice<M, true>(y, lds, sl, W, Ys, p0, nwin, sl.partial + a.mops_off[seq], U)) continue;
+        float best = -FLT_MAX;
+        uint32_t best_i = 0;
+        float* mo = a.mops ? lane_windows(a.mops + a.mops_off[seq], p0, W) : nullptr;
+        for_each_window<M, true>(p0, W, nwin, [&](int m, uint32_t i) {
+            if (mo) mo[m] = U[m];
+            if (U[m] > best) { best = U[m]; best_i = i; }
+        });
+        const WaveMax r = wave_first_max(best, best_i);
+        if (lane == 0) { a.zoops[seq] = r.best; a.z[seq] = r.best_i; }
+    }
+}
+
+template <int M, int THREADS>
+__global__ void __launch_bounds__(THREADS) k_score_tile_slice(ScoreTileArgs a, ScoreSlice sl) {
+    extern __shared__ float lds[];
+    const uint32_t W = a.k.W, Ys = a.k.Y + 1u;
+    load_table(lds, a.k.s + (size_t)sl.j0 * Ys, (sl.j1 - sl.j0) * Ys);
+
+    const int lane = threadIdx.x & 63;
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint32_t waves_per_block = blockDim.x >> 6;
+    const uint32_t total_waves = gridDim.x * waves_per_block;
+
+    for (uint32_t g = blockIdx.x * waves_per_block + wave; g < a.n_tiles; g += total_waves) {
+        const uint32_t t = tile_owner(a.tile_off, a.k.sv.count, g);
+        const uint32_t seq = pick_sequence(a.k.sv, t);
+        const uint32_t L = a.k.sv.len[seq];
+        const uint32_t t0 = (g - a.tile_off[t]) * a.stride;
+        const uint32_t n_emit = min(a.stride, L - W + 1u - t0);   // the tile's windows, in the carrier as in mops
+        uint32_t y[M];
+        decode_tile<M>(a.k.sv, seq, L, a.k.Y, t0, lane, y);
+        const uint32_t p0 = (uint32_t)lane * M;
+        float U[M];
+        if (score_chain_slice<M, false>(y, lds, sl, W, Ys, p0, n_emit, sl.partial + a.k.mops_off[seq] + t0, U)) continue;
+        float best = -FLT_MAX;
+        uint32_t best_i = 0;
+        float* mo = a.k.mops ? lane_windows(a.k.mops + a.k.mops_off[seq] + t0, p0, W) : nullptr;
+        for_each_window<M, false>(p0, W, n_emit, [&](int m, uint32_t i) {
+            if (mo) mo[m] = U[m];
+            if (U[m] > best) { best = U[m]; best_i = t0 + i; }
+        });
+        const WaveMax r = wave_first_max(best, best_i);
+        if (lane == 0) { a.tile_best[g] = r.best; a.tile_idx[g] = r.best_i; }
+    }
+}
+
+// a launch's slice: whole columns of a table that does not fit, inside the motif, its part of the table within the LDS
+bool bad_slice(const ScoreKernelArgs& a, const ScoreSlice& sl, size_t* lds) {
+    *lds = (size_t)(sl.j1 - sl.j0) * (a.Y + 1) * sizeof(float);
+    if (sl.partial && sl.j0 < sl.j1 && sl.j1 <= a.W && *lds <= 160 * 1024 && a.mops_off) return false;
+    set_error("score slice [%u, %u) of W=%u: %zu bytes of LDS, carrier %p", sl.j0, sl.j1, a.W, *lds, (void*)sl.partial);
+    return true;
+}
+
 }  // namespace
+
+int launch_score_slice(int mclass, const ScoreKernelArgs& a, const ScoreSlice& sl, uint32_t blocks, uint32_t threads, hipStream_t st) {
+    size_t lds = 0;
+    if (bad_slice(a, sl, &lds)) return BAMM_ERR_ARG;
+    if (threads > max_threads_for_mclass(mclass) || (threads & 63u) || threads == 0 || blocks == 0) {
+        set_error("bad launch geometry %u x %u for M class %d", blocks, threads, mclass);
+        return BAMM_ERR_ARG;
+    }
+    if (int rc = with_mclass(mclass, [&](auto M, auto T) { return launch_kernel(&k_score_slice<M, T>, blocks, threads, lds, st, a, sl); }))
+        return rc;
+    BAMM_HIP(hipGetLastError());
+    return BAMM_OK;
+}
+
+int launch_score_tiles_slice(const ScoreTileArgs& a, const ScoreSlice& sl, uint32_t blocks, hipStream_t st) {
+    if (a.n_tiles == 0) return BAMM_OK;
+    size_t lds = 0;
+    uint32_t tp = 0, stride = 0;
+    if (bad_slice(a.k, sl, &lds)) return BAMM_ERR_ARG;
+    if (!score_tile_geometry(a.k.W, &tp, &stride) || stride != a.stride || blocks == 0) {
+        set_error("k_score_tile_slice: W=%u, stride %u or %u blocks is outside the tiles' envelope", a.k.W, a.stride, blocks);
+        return BAMM_ERR_ARG;
+    }
+    if (int rc = launch_kernel(&k_score_tile_slice<kTileM, kTileThreads>, blocks, (uint32_t)kTileThreads, lds, st, a, sl)) return rc;
+    BAMM_HIP(hipGetLastError());
+    if (sl.j1 < a.k.W) return BAMM_OK;
+    hipLaunchKernelGGL(k_score_tile_reduce, dim3(std::min((a.k.sv.count + 3u) / 4u, 1024u)), dim3(256), 0, st, a);
+    BAMM_HIP(hipGetLastError());
+    return BAMM_OK;
+}
 
 int launch_score(int mclass, const ScoreKernelArgs& a, uint32_t blocks, uint32_t threads, hipStream_t st) {
     const size_t lds = (size_t)a.W * (a.Y + 1) * sizeof(float);

@@ -646,6 +646,15 @@ def score_tile_geometry(W: int):
     return tp.value, stride.value
 
 
+def score_slice_geometry(K: int, W: int):
+    """(columns_per_slice, slices) of the slices of motif columns the scorer takes a log-odds table of order K and width W in
+    under set_tuning(score_slices=1) (bamm_score_slice_geometry: a pure function, no device needed; slices == 1: the table
+    fits one CU's LDS whole); BammError where not even one column fits."""
+    cps, slices = C.c_uint32(), C.c_uint32()
+    check(abi.load().bamm_score_slice_geometry(K, W, C.byref(cps), C.byref(slices)))
+    return cps.value, slices.value
+
+
 def em_tile_geometry(W: int):
     """(tile_positions, stride) of the tiles an EM pass cuts a sequence beyond 8192 positions into for motifs of width W
     (bamm_em_tile_geometry: a pure function, no device needed); BammError for a W that leaves no stride."""

@@ -46,6 +46,25 @@ bamm_ctx* WarmUp::take(int device_) {
     return c;
 }
 
+namespace {
+
+// The shape classes of profiles/score_slices_ab.txt in which the slices won (the call that downloads zoops and z, which is
+// what this driver's scoring calls do; with the download of every window's score on top no class lost, tiny sets apart):
+//   - a record beyond the length classes, whatever the set (h: 300 x 205 bp + one of 20 kb, 5.6x; e: 16 x 4 M, 204x): the
+//     window-by-window scorer gives such a record to one workgroup
+//   - sets from 30 000 x 205 bp on (g: 1.8x; a: 200 000 x 200 bp, 3.3x; b: K = 4, W = 40, 5.7x).  At 3 000 x 205 bp (f) the
+//     two are level, at 300 x 205 bp (d, the size of the JunD example) two or three launches cost 0.07 ms more than one: the
+//     threshold is g's size, the smallest measured set that wins
+//   - up to order 5.  At order 6 (c: 50 000 x 200 bp, six slices of two columns) the slices' median was 1.4x ahead but
+//     inside the parent's spread of that run: not shown, so order 6 keeps the window-by-window scorer
+bool score_slices_pay(const Options& o, const FastaSet& pos) {
+    constexpr size_t kMinBases = 30000u * 205u;
+    const size_t longest = o.ss ? pos.max_len : 2 * pos.max_len + 1;
+    return o.K <= 5 && (longest > BAMM_MAX_SEQ_POSITIONS || pos.codes.size() >= kMinBases);
+}
+
+}  // namespace
+
 void Run::make_ctx(Dev& dv) {
     if (!dv.ctx) dv.ctx = warm.take(dv.device);             // the one the warm-up made
     if (!dv.ctx && bamm_ctx_create(dv.device, nullptr, &dv.ctx)) die_abi("no usable MI355X");
@@ -53,6 +72,12 @@ void Run::make_ctx(Dev& dv) {
     // (the library reads no environment: the driver turns the variable into the tuning key)
     if (const char* e = std::getenv("BAMM_NO_SCORE_TILES"); e && *e && *e != '0')
         if (bamm_ctx_set_tuning(dv.ctx, "score_tiles", 0)) die_abi("score_tiles");
+    // log-odds tables beyond one CU's LDS (K = 4 from W = 40, K = 5 from W = 10, K = 6 from W = 3) a slice of columns per launch
+    // through the register-resident scorer: off in the library by default, on here where profiles/score_slices_ab.txt shows
+    // the slices ahead of the window-by-window scorer by more than that scorer's own spread; BAMM_NO_SCORE_SLICES=1 keeps the
+    // window-by-window scorer everywhere, the same bytes in every output file
+    const char* e = std::getenv("BAMM_NO_SCORE_SLICES");
+    if (bamm_ctx_set_tuning(dv.ctx, "score_slices", !(e && *e && *e != '0') && score_slices_pay(o, pos) ? 1 : 0)) die_abi("score_slices");
 }
 
 namespace {

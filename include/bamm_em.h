@@ -147,6 +147,12 @@ int  bamm_ctx_set_launch(bamm_ctx* ctx, uint32_t blocks, uint32_t threads_per_bl
  *   "score_tiles"  1/0  the scorer (bamm_logodds*, bamm_occurrences, bamm_fdr_add_set) takes sequences longer than
  *                       BAMM_MAX_SEQ_POSITIONS tile by tile through the register-resident kernel (default 1; 0 = window by
  *                       window, one workgroup per sequence; the same bits); read at the scoring call
+ *   "score_slices" 1/0  the scorer takes a log-odds table beyond one CU's LDS (W * (4^(K+1) + 1) * 4 > 160 KiB) through the same
+ *                       register-resident kernels, a slice of motif columns per launch (bamm_score_slice_geometry; orders up
+ *                       to 6), instead of window by window with the table in global memory; the same bits; read at the
+ *                       scoring call.  Default 0: the library routes as it always has, and the BaMMmotif driver turns the
+ *                       key on for its contexts.  Making 1 the library's default is a one-line change (csrc/handles.h)
+ *                       together with the tests that pin the default plan (tests/test_score_tiles_gpu.py)
  *   "em_tiles"     1/0  EM passes, getR and bamm_em_sites take sequences longer than BAMM_MAX_SEQ_POSITIONS tile by tile
  *                       (csrc/em_tiles.hip) while the handle's odds and count tables fit one CU's LDS unsliced (default 1;
  *                       0 = window by window, one workgroup per sequence: r and counts within a few ulps, see
@@ -173,7 +179,8 @@ long long bamm_device_blocks_live(void);
  * into overlapping tiles, one wavefront per tile on the whole GPU: by EM passes, getR and bamm_em_sites while the handle's
  * tables fit one CU's LDS unsliced (bamm_em_tile_geometry, bamm_em_tile_plan: up to order 3 at usual widths; beyond that
  * window by window, one workgroup per sequence), and by the scorer (bamm_score_tile_geometry) while the log-odds table
- * fits the LDS (W * (4^(K+1) + 1) * 4 <= 160 KiB: up to order 5 at usual widths; window by window beyond that,
+ * fits the LDS (W * (4^(K+1) + 1) * 4 <= 160 KiB: every width up to order 3, K = 4 up to W = 39, K = 5 up to W = 9,
+ * K = 6 up to W = 2; beyond that window by window, or under "score_slices" a slice of columns at a time;
  * bamm_score_plan reports the split) -- the scorer's results are identical on every path, the EM's tile path sums a
  * sequence's partition function in another order (r within 3 ulps of the window-by-window path, deterministic);
  * bamm_seed_from_pwm and bamm_em_mask keep per-wave arrays over one sequence: in LDS up to about
@@ -456,6 +463,12 @@ int  bamm_logodds_subset(bamm_ctx* ctx, bamm_seqs* seqs, const uint8_t* seq_mask
  * up to window L - W.  Pure host arithmetic, no device needed; either pointer may be NULL.  BAMM_ERR_ARG for W = 0 and
  * for a W that leaves no stride of at least 16 (such motifs are scored window by window).                          */
 int  bamm_score_tile_geometry(uint32_t W, uint32_t* tile_positions, uint32_t* stride);
+/* The slices of motif columns the scorer cuts a log-odds table of order K and width W into under "score_slices" = 1:
+ * cmax = floor(163840 / ((4^(K+1) + 1) * 4)) columns fit one CU's LDS, *slices = ceil(W / cmax), *columns_per_slice =
+ * ceil(W / slices) (balanced; the last slice may be shorter).  slices == 1: the table fits whole.  Pure host arithmetic, no
+ * device needed; either pointer may be NULL.  BAMM_ERR_ARG for W = 0, K > BAMM_MAX_ORDER and where not one column fits
+ * (orders 7..10, which are scored window by window whatever the key says).                                          */
+int  bamm_score_slice_geometry(uint32_t K, uint32_t W, uint32_t* columns_per_slice, uint32_t* slices);
 /* Which kernel the scorer takes for the sequences of `seqs` with a model of order K and width W, under the context's
  * tuning as it stands: sequences held in one wavefront's registers, sequences cut into tiles (and the number of tiles,
  * without a sequence mask), sequences walked window by window with the table in global memory.  Any pointer may be NULL. */
