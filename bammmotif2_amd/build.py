@@ -15,7 +15,7 @@ import subprocess
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libbamm_em.so")
-SOURCES = ["model.hip", "kernels.hip", "grouped.hip", "grouped_long.hip", "grouped_xl.hip", "grouped_mix.hip", "grouped_mix1.hip", "lane_records.hip", "mask.hip", "seed.hip", "long_seq.hip", "scorer.hip", "em_tiles.hip", "prep.hip", "negs.hip", "occ.hip", "sites.hip", "fdr.hip", "ctx.cpp", "seqs.cpp", "negs.cpp", "plan.cpp", "em_pass.cpp", "em.cpp",
+SOURCES = ["model.hip", "kernels.hip", "grouped.hip", "grouped_long.hip", "grouped_xl.hip", "grouped_mix.hip", "grouped_mix1.hip", "lane_records.hip", "mask.hip", "seed.hip", "long_seq.hip", "scorer.hip", "em_tiles.hip", "prep.hip", "negs.hip", "occ.hip", "sites.hip", "fdr.hip", "kmer_count.hip", "ctx.cpp", "seqs.cpp", "kmer_count.cpp", "negs.cpp", "plan.cpp", "em_pass.cpp", "em.cpp",
            "score.cpp", "occurrences.cpp", "sites.cpp", "fdr_stats.cpp", "comm.cpp", "pack.cpp"]
 HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "device_utils.h"), os.path.join(CSRC, "mclass.h"), os.path.join(CSRC, "tiles.h"), os.path.join(CSRC, "grouped_kernel.h"), os.path.join(CSRC, "mixed_kernel.h"), os.path.join(CSRC, "lane_records.h"), os.path.join(CSRC, "update_kernel.h"), os.path.join(CSRC, "phase_clock.h"),
            os.path.join(HERE, "..", "include", "bamm_em.h")]
@@ -128,15 +128,16 @@ def _stale(target: str, deps) -> bool:
 
 # headers only some translation units include (a change there does not rebuild the sequence kernels); handles.h, which
 # includes prep.h, is the private header of the C ABI's host units
-_HANDLES = [os.path.join(CSRC, "handles.h"), os.path.join(CSRC, "prep.h")]
+_HANDLES = [os.path.join(CSRC, "handles.h"), os.path.join(CSRC, "prep.h"), os.path.join(CSRC, "packed_set.h")]
 EXTRA_DEPS = {"prep.hip": [os.path.join(CSRC, "prep.h")], "negs.hip": [os.path.join(CSRC, "negs.h")],
               "ctx.cpp": _HANDLES, "plan.cpp": _HANDLES, "em_pass.cpp": _HANDLES, "em.cpp": _HANDLES, "score.cpp": _HANDLES, "sites.cpp": _HANDLES,
               "occurrences.cpp": _HANDLES + [os.path.join(CSRC, "occ_pvalue.h")],
               "fdr.hip": [os.path.join(CSRC, "fdr_rows.h"), os.path.join(CSRC, "sort_key.h")], "occ.hip": [os.path.join(CSRC, "sort_key.h")],
               "fdr_stats.cpp": _HANDLES + [os.path.join(CSRC, "fdr_rows.h")],
               "seqs.cpp": _HANDLES,
+              "kmer_count.hip": [os.path.join(CSRC, "kmer_count.h")], "kmer_count.cpp": _HANDLES + [os.path.join(CSRC, "kmer_count.h")],
               "negs.cpp": _HANDLES + [os.path.join(CSRC, f) for f in ("negs.h", "glibc_rand.h", "neg_layout.h", "packed_set.h")],
-              "pack.cpp": [os.path.join(CSRC, "glibc_rand.h"), os.path.join(CSRC, "prep.h")]}
+              "pack.cpp": [os.path.join(CSRC, "glibc_rand.h"), os.path.join(CSRC, "prep.h"), os.path.join(CSRC, "packed_set.h")]}
 FLAGS_STAMP = os.path.join(OBJDIR, "flags.txt")
 
 
@@ -225,7 +226,7 @@ HOST_LIB = os.path.join(HERE, "libbamm_host.so")
 CLI = os.path.join(HERE, "BaMMmotif")
 # one list per product, from which both the compile lines and the staleness check are derived: io.cpp / fdr.cpp and the
 # slot plan are in both, hooks.cpp is the test hooks' own, the other units are the CLI driver (host/driver.h)
-HOST_SHARED = ["io.cpp", "fdr.cpp", "slot_plan.cpp"]
+HOST_SHARED = ["io.cpp", "fdr.cpp", "slot_plan.cpp", "seeder.cpp"]
 HOST_SOURCES = HOST_SHARED + ["hooks.cpp"]
 CLI_SOURCES = ["main.cpp", "options.cpp", "context.cpp", "negatives.cpp", "em_run.cpp", "score.cpp", "folds.cpp"] + HOST_SHARED
 HOST_HEADERS = ["bamm_host.h", "host_util.h", "row_text.h", "neg_sampler.h", "slot_plan.h", "options.h", "driver.h"]

@@ -239,6 +239,8 @@ const TuningKey kTuningKeys[] = {
     {"list_threshold_pct", &bamm_ctx::list_threshold_pct, 0, 100, 0, "0..100"},
     {"sites_chunk_positions", &bamm_ctx::sites_chunk_positions, 0, INT_MAX, 0, ">= 0"},
     {"neg_segment_positions", &bamm_ctx::neg_segment_positions, 16, 1 << 20, 0, "0 (default) or 16..1048576"},
+    {"kmer_segment_positions", &bamm_ctx::kmer_segment_positions, 16, 1 << 20, 0, "0 (default) or 16..1048576"},
+    {"kmer_flush_windows", &bamm_ctx::kmer_flush_windows, 1, INT_MAX, 0, "0 (default) or >= 1"},
     {"group_size", &bamm_ctx::group_size, 2, 4, 0, "0 (auto) or 2..4"},
     {"group_layout", &bamm_ctx::group_layout, -1, 3, 8, "-1 (auto), 0..3 or 8 (mixed rows)"},
 };

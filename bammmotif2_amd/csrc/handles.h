@@ -18,6 +18,7 @@
 #include <unordered_map>
 
 #include "common.h"
+#include "packed_set.h"
 #include "prep.h"
 
 // the longest length class (positions per lane) whose grouped kernels are built with the fused-update prologue and the
@@ -174,6 +175,8 @@ struct bamm_ctx {
     size_t scratch_idle_bytes = 0, scratch_cap_bytes = 0;
     uint32_t sites_chunk_positions = 0;                      // bamm_em_sites: dense r kept on the device at a time (0 = default)
     uint32_t neg_segment_positions = 0;                      // bamm_sample_negatives: positions per segment of a long record, rounded down to 16s (0 = default)
+    uint32_t kmer_segment_positions = 0;                     // bamm_kmer_counts: positions per segment of a record longer than that, rounded down to 16s (0 = default)
+    uint32_t kmer_flush_windows = 0;                         // bamm_kmer_counts: a workgroup flushes its LDS table once it has added this many windows (0 = default)
     bool scratch_poison = false;                             // tests: every block is filled with 0xFF when it is handed out
     uint64_t scratch_hits = 0, scratch_misses = 0;
     // Every transfer of 64 KiB or more between the CALLER's memory and the device goes through this pinned area (two chunks,
@@ -259,6 +262,12 @@ struct bamm_seqs {
     bamm::RawVec<uint32_t> h_exc_pos, h_exc_kmer, h_exc_clean;
     std::vector<bamm::Bucket> buckets;
     std::map<uint32_t, bamm::ExcK> exc_by_order;   // node-based: pointers into it stay valid
+    // the unknown forward positions of a set built from codes (packed_set.h; null: built from kmer_ arrays), record 0 of the
+    // set being record unk_begin of the list; on the device from the first bamm_kmer_counts on (under `mu`)
+    std::shared_ptr<const bamm::UnknownList> unk;
+    uint64_t unk_begin = 0;
+    uint64_t* d_unk_off = nullptr;              // [n + 1], rebased to the set's first record
+    uint32_t* d_unk_pos = nullptr;
 };
 
 struct bamm_em : bamm::EmBook {                 // (the fields an update moves: d_s, d_q, d_v, d_acc, ... -- see EmBook)

@@ -13,10 +13,13 @@
 #include <cstdarg>
 #include <cstdlib>
 #include <cstring>
+#include <mutex>
 #include <new>
+#include <unordered_map>
 
 #include "common.h"
 #include "glibc_rand.h"
+#include "packed_set.h"
 
 namespace bamm {
 
@@ -76,6 +79,7 @@ size_t bamm_bg_size(uint32_t K) { return bg_size(K); }
 
 void bamm_packed_free(bamm_packed* p) {
     if (!p) return;
+    packed_forget_unknowns(p);
     free(p->words);
     free(p->word_off);
     free(p->len);
@@ -357,6 +361,7 @@ static int pack_codes_impl(const uint8_t* codes, const uint64_t* off, uint64_t n
         b.eclean.insert(b.eclean.end(), loc[t].eclean.begin(), loc[t].eclean.end());
     }
     *out = b.finish();
+    packed_note_unknowns(*out, unknowns_of_codes(codes, off, n_seqs, single_strand != 0));
     return BAMM_OK;
 }
 
@@ -518,6 +523,97 @@ int bamm_calculate_p(const float* v, const float* vbg, uint32_t bg_order, uint32
             for (uint32_t j = k; j < W; j++) pk[y * W + j] = vk[y * W + j] * pk1[(y / 4) * W + j - 1];
         }
     }
+    return BAMM_OK;
+}
+
+}  // extern "C"
+
+// ---- the unknown positions of a set built from codes (packed_set.h) -------------------------------------------------------
+namespace bamm {
+namespace {
+std::mutex g_unknowns_mu;
+// (never destroyed: a packed set may be freed from a static destructor of the caller's)
+std::unordered_map<const bamm_packed*, std::shared_ptr<const UnknownList>>& unknowns_by_set() {
+    static auto* m = new std::unordered_map<const bamm_packed*, std::shared_ptr<const UnknownList>>();
+    return *m;
+}
+}  // namespace
+
+std::shared_ptr<const UnknownList> unknowns_of_codes(const uint8_t* codes, const uint64_t* off, uint64_t n_seqs, bool single_strand) {
+    auto list = std::make_shared<UnknownList>();
+    list->single_strand = single_strand;
+    list->off.assign(n_seqs + 1, 0);
+    const uint32_t T = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(host_threads(), n_seqs / 16384 + 1));
+    auto each_zero = [&](uint64_t n, auto&& fn) {
+        const uint8_t* c = codes + off[n];
+        const size_t L0 = (size_t)(off[n + 1] - off[n]);
+        for (const uint8_t* z = (const uint8_t*)memchr(c, 0, L0); z; z = (const uint8_t*)memchr(z + 1, 0, (size_t)(c + L0 - z - 1))) fn((uint32_t)(z - c));
+    };
+    parallel_ranges(n_seqs, T, [&](uint32_t, uint64_t n0, uint64_t n1) {
+        for (uint64_t n = n0; n < n1; n++) { uint64_t k = 0; each_zero(n, [&](uint32_t) { k++; }); list->off[n + 1] = k; }
+    });
+    for (uint64_t n = 0; n < n_seqs; n++) list->off[n + 1] += list->off[n];
+    list->pos.resize(list->off[n_seqs]);
+    if (!list->pos.empty())
+        parallel_ranges(n_seqs, T, [&](uint32_t, uint64_t n0, uint64_t n1) {
+            for (uint64_t n = n0; n < n1; n++) { uint64_t at = list->off[n]; each_zero(n, [&](uint32_t z) { list->pos[at++] = z; }); }
+        });
+    return list;
+}
+
+void packed_note_unknowns(const bamm_packed* p, std::shared_ptr<const UnknownList> list) {
+    if (!p) return;
+    std::lock_guard<std::mutex> g(g_unknowns_mu);
+    unknowns_by_set()[p] = std::move(list);
+}
+
+std::shared_ptr<const UnknownList> packed_unknowns(const bamm_packed* p) {
+    std::lock_guard<std::mutex> g(g_unknowns_mu);
+    auto it = unknowns_by_set().find(p);
+    return it == unknowns_by_set().end() ? nullptr : it->second;
+}
+
+void packed_forget_unknowns(const bamm_packed* p) {
+    std::lock_guard<std::mutex> g(g_unknowns_mu);
+    unknowns_by_set().erase(p);
+}
+}  // namespace bamm
+
+extern "C" {
+
+// The host twin of bamm_kmer_counts (csrc/kmer_count.hip): the same table from the FASTA codes, a rolling window and its
+// reverse complement per record, ranges of records on the host threads with a table each, summed at the end.
+int bamm_kmer_counts_host(const uint8_t* codes, const uint64_t* off, uint64_t n_seqs, int single_strand, uint32_t w,
+                          uint64_t* counts, uint64_t* n_windows) {
+    if (!counts || (n_seqs && (!codes || !off))) { set_error("bamm_kmer_counts_host: null argument"); return BAMM_ERR_ARG; }
+    if (w < 6 || w > 8) { set_error("bamm_kmer_counts_host: w = %u outside 6..8", w); return BAMM_ERR_ARG; }
+    const size_t cells = ipow4(w);
+    const uint32_t mask = (uint32_t)cells - 1u, top = 2u * (w - 1u);
+    const uint32_t T = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(host_threads(), n_seqs / 1024 + 1));
+    std::vector<std::vector<uint64_t>> part(T, std::vector<uint64_t>(cells, 0));
+    parallel_ranges(n_seqs, T, [&](uint32_t t, uint64_t n0, uint64_t n1) {
+        uint64_t* mine = part[t].data();
+        for (uint64_t n = n0; n < n1; n++) {
+            uint32_t y = 0, rc = 0, run = 0;                 // run: codes since the last unknown one
+            for (uint64_t i = off[n]; i < off[n + 1]; i++) {
+                const uint32_t c = codes[i];
+                if (c < 1u || c > 4u) { run = 0; continue; }
+                y = ((y << 2) | (c - 1u)) & mask;
+                rc = (rc >> 2) | ((4u - c) << top);
+                if (++run < w) continue;
+                mine[y]++;
+                if (!single_strand) mine[rc]++;
+            }
+        }
+    });
+    uint64_t total = 0;
+    for (size_t y = 0; y < cells; y++) {
+        uint64_t c = 0;
+        for (uint32_t t = 0; t < T; t++) c += part[t][y];
+        counts[y] = c;
+        total += c;
+    }
+    if (n_windows) *n_windows = total;
     return BAMM_OK;
 }
 

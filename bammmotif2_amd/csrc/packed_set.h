@@ -4,6 +4,7 @@
 #pragma once
 #include <cstdlib>
 #include <memory>
+#include <vector>
 
 #include "../../include/bamm_em.h"
 
@@ -37,6 +38,25 @@ inline int packed_alloc(uint64_t n_seqs, uint64_t n_words, uint64_t n_exc, Packe
     *out = std::move(p);
     return BAMM_OK;
 }
+
+// Where the unknown bases of a set built from FASTA codes were: per record the FORWARD positions that held code 0, ascending.
+// The exception list cannot tell (it marks every position whose 11-mer is tainted and carries the byte-'N' quirk of the
+// reverse strand), so the makers that see the codes (bamm_pack_codes*) note the list beside the
+// bamm_packed they return -- the public struct keeps its layout; the note is kept by the packed set's address until
+// bamm_packed_free -- and bamm_seqs_upload hands it to the resident set.  Sets packed from kmer_ arrays have none.
+// Invariant of the note: every bamm_packed the library hands out is released through bamm_packed_free, which forgets the
+// note before the memory goes back (include/bamm_em.h says so).  A struct copied by value has no note (its address differs);
+// the library's own makers that do not see codes (pack_impl, packed_alloc) return fresh calloc blocks, whose addresses can
+// only repeat one that bamm_packed_free has already forgotten.
+struct UnknownList {
+    bool single_strand = false;
+    std::vector<uint64_t> off;   // [n_seqs + 1]
+    std::vector<uint32_t> pos;   // [off[n_seqs]]
+};
+std::shared_ptr<const UnknownList> unknowns_of_codes(const uint8_t* codes, const uint64_t* off, uint64_t n_seqs, bool single_strand);   // pack.cpp, like the three below
+void packed_note_unknowns(const bamm_packed* p, std::shared_ptr<const UnknownList> list);
+std::shared_ptr<const UnknownList> packed_unknowns(const bamm_packed* p);                  // null: none noted
+void packed_forget_unknowns(const bamm_packed* p);
 
 // The length rule: 16 positions per 32-bit word, every sequence on a word boundary.  From p->n_seqs lengths (`lens` may
 // be p->len itself) it fills len, word_off, n_words, total_len, max_len and min_len (0 for an empty set).  exc_off is

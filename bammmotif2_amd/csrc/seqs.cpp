@@ -222,7 +222,12 @@ static int seqs_upload_impl(bamm_ctx* c, const bamm_packed* p, uint64_t begin, u
 }
 
 int bamm_seqs_upload(bamm_ctx* c, const bamm_packed* p, uint64_t begin, uint64_t end, bamm_seqs** out) {
-    return seqs_upload_impl(c, p, begin, end, out, nullptr);
+    const int rc = seqs_upload_impl(c, p, begin, end, out, nullptr);
+    if (!rc) {                                               // where the set's unknown bases were, if its maker noted it (packed_set.h)
+        (*out)->unk = packed_unknowns(p);
+        (*out)->unk_begin = begin;
+    }
+    return rc;
 }
 
 // bamm_pack_codes_seeded on the device (csrc/prep.hip), then bamm_seqs_upload: the same packed set, the same resident set

@@ -603,6 +603,58 @@ def sample_negatives(ctx: Context, positives: SeqSet, s_order: int = 2, m_fold: 
     return packed, neg
 
 
+def kmer_counts(ctx: Context, seqs: SeqSet, w: int):
+    """The exact w-mer table of a resident set built from codes, w = 6..8 (bamm_kmer_counts): (counts uint64 [4^w], their
+    sum).  A w-mer's cell is its bases as a base-4 number, oldest base most significant."""
+    counts = np.zeros(4 ** max(int(w), 0) if 0 <= int(w) <= 8 else 1, np.uint64)
+    total = C.c_uint64(0)
+    check(ctx.lib.bamm_kmer_counts(ctx.h, seqs.h, int(w), counts, C.byref(total)))
+    return counts, int(total.value)
+
+
+def kmer_counts_host(codes, off, w: int, single_strand: bool = False):
+    """The same table from the FASTA codes, on the host threads (bamm_kmer_counts_host)."""
+    off = _u64(off)
+    counts = np.zeros(4 ** max(int(w), 0) if 0 <= int(w) <= 8 else 1, np.uint64)
+    total = C.c_uint64(0)
+    check(abi.load().bamm_kmer_counts_host(np.ascontiguousarray(codes, np.uint8), off, len(off) - 1, int(single_strand), int(w),
+                                           counts, C.byref(total)))
+    return counts, int(total.value)
+
+
+_host_lib = None
+
+
+def _host():
+    """libbamm_host.so: the C++ host code behind the BaMMmotif driver (its seeder is what kmer_seeds calls)."""
+    global _host_lib
+    if _host_lib is None:
+        from . import build
+        build.build_host()                                    # (a no-op when the library is up to date)
+        H = C.CDLL(build.HOST_LIB)
+        H.bh_last_error.restype = C.c_char_p
+        _host_lib = H
+    return _host_lib
+
+
+def kmer_seeds(counts, n_windows: int, vbg, Kbg: int, w: int, max_seeds: int = 4, single_strand: bool = False):
+    """The seeds the BaMMmotif driver takes from a w-mer table under --seedKmers (host/seeder.cpp): (w-mers uint32 [n],
+    z-scores float64 [n], PWMs float32 [n][4][w]) in rank order; vbg: the background model of order Kbg, flat [k][y]."""
+    H = _host()
+    counts, vbg = _u64(counts), _f32(vbg)
+    assert len(counts) == 4 ** w and len(vbg) >= bg_size(Kbg)
+    cap = max(int(max_seeds), 1)
+    n = C.c_uint32(0)
+    kmer, cnt, z = np.zeros(cap, np.uint32), np.zeros(cap, np.uint64), np.zeros(cap, np.float64)
+    pwm = np.zeros((cap, 4, w), np.float32)
+    if H.bh_kmer_seeds(counts.ctypes.data_as(C.c_void_p), C.c_uint64(int(n_windows)), C.c_uint32(w), C.c_uint32(Kbg),
+                       vbg.ctypes.data_as(C.c_void_p), C.c_uint64(int(max_seeds)), C.c_int(int(single_strand)), C.byref(n),
+                       kmer.ctypes.data_as(C.c_void_p), cnt.ctypes.data_as(C.c_void_p), z.ctypes.data_as(C.c_void_p),
+                       pwm.ctypes.data_as(C.c_void_p)):
+        raise RuntimeError(H.bh_last_error().decode(errors="replace"))
+    return kmer[: n.value].copy(), z[: n.value].copy(), pwm[: n.value].copy()
+
+
 def seed_from_pwm(ctx: Context, seqs: SeqSet, K: int, W: int, score, q: float, u):
     """The pass over the sequences of Motif::initFromPWM (Motif.cpp:228-311) on the device: returns
     (counts[v_size(K,W)] int32, z[n_seqs] uint32).  score: [4][W] floored PWM / 0th-order background;

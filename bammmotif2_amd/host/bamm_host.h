@@ -81,10 +81,35 @@ struct SeedSet {
     std::vector<Motif> motifs;
     uint32_t max_w = 0;
 };
+// the MEME reader of load_seeds (MotifSet.cpp:62-117): each(width incl. flanks, q, pwm [4][width]) per motif, in file order;
+// it returns 0 to go on, 1 on an error of its own (err set), 2 to stop reading
+int read_meme_pwms(const std::string& path, uint32_t l_flank, uint32_t r_flank, float glob_q, std::string& err,
+                   const std::function<int(uint32_t, float, const std::vector<float>&)>& each);
 // MotifSet::MotifSet (MotifSet.cpp:3-222); tag = "PWM" | "BaMM" | "bindingsites"
 int load_seeds(const std::string& path, const std::string& tag, uint32_t l_flank, uint32_t r_flank, uint32_t K,
                const std::vector<float>& alpha, size_t max_pwm, float glob_q, const BgModel& bg, const uint32_t* yK,
                const uint64_t* off, size_t n_seqs, SeedSet& out, std::string& err, const SeedDevice* dev = nullptr);
+
+// ---- de novo seeds from exact w-mer counts (seeder.cpp; --seedKmers, no counterpart in the reference) ----
+// counts[4^w]: bamm_kmer_counts' table (a w-mer as a base-4 number, oldest base most significant), n_windows its sum.
+//   P(y)  = product over the window's positions i of the background's conditional probability at order min(i, bg.K)
+//   E(y)  = n_windows * (P(y) + P(rc y)) / 2, or n_windows * P(y) single-stranded;  z(y) = (counts[y] - E) / sqrt(E)
+// Cells are visited in descending z (ties: the smaller y first) and taken unless the cell or -- both strands -- its reverse
+// complement is within Hamming distance 1 of a w-mer already taken; the walk stops at max_seeds seeds or at the first
+// z <= 0.  A seed's PWM: column j, base b = the counts of the w-mer and of its 3 w Hamming-1 neighbours that carry b at j,
+// + 1, normalised per column; double arithmetic on the integers, rounded to float once.
+struct KmerSeed {
+    uint32_t kmer = 0;
+    uint64_t count = 0;
+    double z = 0;
+    std::vector<float> pwm;             // [4][w], pwm[b * w + j]
+};
+void kmer_seeds(const uint64_t* counts, uint64_t n_windows, uint32_t w, const BgModel& bg, size_t max_seeds, bool ss,
+                std::vector<KmerSeed>& out);
+std::string kmer_string(uint32_t kmer, uint32_t w);
+// the seeds as a MEME file load_seeds(tag "PWM") reads back to the same floats: one motif per seed, the w-mer, its count
+// and its z-score in the motif's name line
+int kmer_seeds_write(const std::string& path, uint32_t w, const std::vector<KmerSeed>& seeds, std::string& err);
 
 // =============================================== negatives ==============================================
 // every core the process may use (affinity mask capped by the cgroup quota): for host work whose result does not

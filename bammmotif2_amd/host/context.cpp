@@ -94,7 +94,9 @@ void read_and_pack(Run& run, std::vector<uint64_t>& off, bamm_seqs*& dseqs_all) 
     run.devs.resize(o.need_gpu() ? o.device_list.size() : 1);
     for (size_t d = 0; d < run.devs.size(); d++) run.devs[d].device = o.device_list[d];
     // the stream stands at srand(42) (main(); nothing between draws from it): the N draws are taken on all host threads
-    if (o.need_gpu() && !o.hostPacking) {
+    // (--seedKmers packs on the host: the w-mer counter needs to know where the unknown bases were, which a packed set
+    // notes when bamm_pack_codes* makes it; bamm_seqs_from_codes does not)
+    if (o.need_gpu() && !o.hostPacking && !o.seedKmers) {
         // Sequence::Sequence where the data will live (csrc/prep.hip): the same packed set, and the resident set with it
         run.make_ctx(run.devs[0]);
         if (bamm_seqs_from_codes(run.devs[0].ctx, pos.codes.data(), pos.off.data(), pos.size(), o.ss ? 1 : 0, 42u, &run.packed, &dseqs_all)) die_abi("packing sequences");
@@ -125,11 +127,39 @@ void background_model(Run& run, bamm_seqs* dseqs_all) {
     run.stage("background model");
 }
 
+// --seedKmers: the exact w-mer table of the positives (on the device over the resident set, or with --hostSeedCounts / without
+// a GPU stage on the host threads: the same integers), ranked against the background model (seeder.cpp), written as
+// OUTDIR/<basename>_seeds.meme.  seed_models() then reads that file like any --PWMFile: there is no second seeding path.
+void kmer_seed_file(Run& run, bamm_seqs*& dseqs_all) {
+    const Options& o = run.o;
+    const uint32_t w = o.seedKmers;
+    std::vector<uint64_t> counts(size_t(1) << (2 * w));
+    uint64_t n_windows = 0;
+    if (o.need_gpu() && !o.hostSeedCounts) {
+        run.make_ctx(run.devs[0]);
+        if (!dseqs_all && bamm_seqs_upload(run.devs[0].ctx, run.packed, 0, run.packed->n_seqs, &dseqs_all)) die_abi("upload");
+        if (bamm_kmer_counts(run.devs[0].ctx, dseqs_all, w, counts.data(), &n_windows)) die_abi("w-mer counts");
+        run.stage("w-mer counts on the device (--seedKmers)");
+    } else {
+        if (bamm_kmer_counts_host(run.pos.codes.data(), run.pos.off.data(), run.pos.size(), o.ss ? 1 : 0, w, counts.data(), &n_windows)) die_abi("w-mer counts");
+        run.stage("w-mer counts on the host (--seedKmers)");
+    }
+    std::vector<KmerSeed> seeds;
+    std::string err;
+    kmer_seeds(counts.data(), n_windows, w, run.bg, o.maxPWM, o.ss, seeds);
+    if (seeds.empty()) die("Error: --seedKmers found no " + std::to_string(w) + "-mer that is more frequent than the background model expects.");
+    if (kmer_seeds_write(o.seed_file, w, seeds, err)) die(err);
+    if (o.verbose)
+        for (const KmerSeed& s : seeds) std::cout << "seed " << kmer_string(s.kmer, w) << "  count " << s.count << "  z " << s.z << std::endl;
+    run.stage("rank w-mers, write the seed file");
+}
+
 void seed_models(Run& run, const std::vector<uint64_t>& off, bamm_seqs*& dseqs_all, std::vector<uint8_t>& keep) {
     const Options& o = run.o;
     const bamm_packed* packed = run.packed;
     const size_t N = run.pos.size();
     std::string err;
+    if (o.seedKmers) kmer_seed_file(run, dseqs_all);
     SeedDevice seed_dev;
     std::vector<uint32_t> yK;
     if (o.need_gpu() && o.seed_tag == "PWM" && !o.hostSeeding) {

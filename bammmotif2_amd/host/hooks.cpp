@@ -125,6 +125,47 @@ int bh_load_seed_dev(const char* path, const char* tag, uint32_t l_flank, uint32
                           w_out, q_out, v_out, v_cap, &dev);
 }
 
+// ---- de novo seeds (seeder.cpp) ----
+// kmer_seeds on a caller-provided table: *n_out seeds (at most max_seeds); kmer / count / z hold max_seeds entries, pwm
+// max_seeds x [4][w]
+int bh_kmer_seeds(const uint64_t* counts, uint64_t n_windows, uint32_t w, uint32_t bg_order, const float* vbg, uint64_t max_seeds,
+                  int ss, uint32_t* n_out, uint32_t* kmer, uint64_t* count, double* z, float* pwm) {
+    std::vector<KmerSeed> seeds;
+    kmer_seeds(counts, n_windows, w, bg_from(bg_order, vbg), (size_t)max_seeds, ss != 0, seeds);
+    *n_out = (uint32_t)seeds.size();
+    for (size_t i = 0; i < seeds.size(); i++) {
+        kmer[i] = seeds[i].kmer; count[i] = seeds[i].count; z[i] = seeds[i].z;
+        memcpy(pwm + i * 4 * (size_t)w, seeds[i].pwm.data(), 4 * (size_t)w * sizeof(float));
+    }
+    return 0;
+}
+
+int bh_kmer_seeds_write(const char* path, uint32_t w, uint32_t n, const uint32_t* kmer, const uint64_t* count, const double* z, const float* pwm) {
+    std::vector<KmerSeed> seeds(n);
+    for (uint32_t i = 0; i < n; i++) {
+        seeds[i].kmer = kmer[i]; seeds[i].count = count[i]; seeds[i].z = z[i];
+        seeds[i].pwm.assign(pwm + i * 4 * (size_t)w, pwm + (i + 1) * 4 * (size_t)w);
+    }
+    return kmer_seeds_write(path, w, seeds, g_err);
+}
+
+// the MEME reader of load_seeds on its own: motif `index` of the file as [4][*w_out] floats; *n_motifs = motifs in the file
+int bh_read_meme_pwm(const char* path, uint32_t index, uint32_t* n_motifs, uint32_t* w_out, float* pwm_out, uint64_t pwm_cap) {
+    uint32_t seen = 0;
+    int bad = 0;
+    if (read_meme_pwms(path, 0, 0, 0.3f, g_err, [&](uint32_t W, float, const std::vector<float>& pwm) {
+            if (seen++ == index) {
+                if (pwm.size() > pwm_cap) { g_err = "pwm buffer too small"; bad = 1; return 1; }
+                *w_out = W;
+                memcpy(pwm_out, pwm.data(), pwm.size() * sizeof(float));
+            }
+            return 0;
+        })) return 1;
+    *n_motifs = seen;
+    if (index >= seen) { g_err = "motif index out of range"; return 1; }
+    return bad;
+}
+
 // OpenMP threads of the host-side loops (the CLI's --threads)
 void bh_set_threads(int n) { omp_set_num_threads(n > 0 ? n : 1); set_host_parallelism(n > 0 ? n : 1); }
 void bh_auto_threads() { set_host_parallelism(0); }

@@ -457,6 +457,45 @@ int motif_write(const std::string& dir, const std::string& basename, const Motif
 }
 
 // -------------------------------------------------------------------------------- seeds ----
+int read_meme_pwms(const std::string& path, uint32_t l_flank, uint32_t r_flank, float glob_q, std::string& err,
+                   const std::function<int(uint32_t, float, const std::vector<float>&)>& each) {
+    std::ifstream file(path.c_str());
+    if (!file.good()) { err = "Error: Cannot open PWM file: " + path; return 1; }
+    std::string line, row;
+    size_t seen = 0;
+    while (std::getline(file, line)) {
+        if (line.find("letter-probability matrix") == std::string::npos) continue;   // MotifSet.cpp:71
+        size_t asize = 0, length = 0;
+        float q = glob_q;
+        { std::stringstream s(line.substr(line.find("h=") + 2)); s >> asize; }
+        { std::stringstream s(line.substr(line.find("w=") + 2)); s >> length; }
+        if (line.find("occur=") != std::string::npos) {
+            std::stringstream s(line.substr(line.find("occur=") + 7));               // MotifSet.cpp:86 (+7 as is)
+            s >> q;
+        }
+        if (asize != 4) { err = "Error: only the STANDARD alphabet (alength= 4) is supported: " + path; return 1; }
+        length += l_flank + r_flank;
+        std::vector<float> pwm(4 * length, 0.25f);
+        for (size_t j = l_flank; j + r_flank < length; j++) {
+            if (!std::getline(file, row)) {
+                err = "Error: Cannot find any PWM in the MEME-format file: " + path + "\nPlease check the content of your input MEME file.";
+                return 1;
+            }
+            std::stringstream number(row);
+            for (size_t y = 0; y < 4; y++) number >> pwm[y * length + j];
+        }
+        seen++;
+        const int rc = each((uint32_t)length, q, pwm);
+        if (rc == 1) return 1;
+        if (rc == 2) break;
+    }
+    if (!seen) {
+        err = "Error: Cannot find any PWM in the MEME-format file: " + path + "\nPlease check the version of your input MEME file.";
+        return 1;
+    }
+    return 0;
+}
+
 int load_seeds(const std::string& path, const std::string& tag, uint32_t l_flank, uint32_t r_flank, uint32_t K,
                const std::vector<float>& alpha, size_t max_pwm, float glob_q, const BgModel& bg, const uint32_t* yK,
                const uint64_t* off, size_t n_seqs, SeedSet& out, std::string& err, const SeedDevice* dev) {
@@ -474,41 +513,14 @@ int load_seeds(const std::string& path, const std::string& tag, uint32_t l_flank
         return 0;
     }
     if (tag == "PWM") {
-        if (!file.good()) { err = "Error: Cannot open PWM file: " + path; return 1; }
-        std::string line, row;
-        while (std::getline(file, line)) {
-            if (line.find("letter-probability matrix") == std::string::npos) continue;   // MotifSet.cpp:71
-            size_t asize = 0, length = 0;
-            float q = glob_q;
-            { std::stringstream s(line.substr(line.find("h=") + 2)); s >> asize; }
-            { std::stringstream s(line.substr(line.find("w=") + 2)); s >> length; }
-            if (line.find("occur=") != std::string::npos) {
-                std::stringstream s(line.substr(line.find("occur=") + 7));               // MotifSet.cpp:86 (+7 as is)
-                s >> q;
-            }
-            if (asize != 4) { err = "Error: only the STANDARD alphabet (alength= 4) is supported: " + path; return 1; }
-            length += l_flank + r_flank;
+        return read_meme_pwms(path, l_flank, r_flank, glob_q, err, [&](uint32_t length, float q, const std::vector<float>& pwm) {
             Motif m;
-            motif_alloc(m, (uint32_t)length, K, alpha, q);
-            std::vector<float> pwm(4 * length, 0.25f);
-            for (size_t j = l_flank; j + r_flank < length; j++) {
-                if (!std::getline(file, row)) {
-                    err = "Error: Cannot find any PWM in the MEME-format file: " + path + "\nPlease check the content of your input MEME file.";
-                    return 1;
-                }
-                std::stringstream number(row);
-                for (size_t y = 0; y < 4; y++) number >> pwm[y * length + j];
-            }
+            motif_alloc(m, length, K, alpha, q);
             if (motif_init_from_pwm(m, pwm, bg, yK, off, n_seqs, q, dev, err)) return 1;
             out.max_w = std::max(out.max_w, m.W);
             out.motifs.push_back(std::move(m));
-            if (out.motifs.size() >= max_pwm) break;
-        }
-        if (out.motifs.empty()) {
-            err = "Error: Cannot find any PWM in the MEME-format file: " + path + "\nPlease check the version of your input MEME file.";
-            return 1;
-        }
-        return 0;
+            return out.motifs.size() >= max_pwm ? 2 : 0;
+        });
     }
     if (tag == "BaMM") {
         if (!file.good()) { err = "Error: Cannot open BaMM file: " + path; return 1; }

@@ -2,7 +2,8 @@
 // The EM itself runs on the GPU through the C ABI (include/bamm_em.h); everything here is host plumbing with the reference's
 // flags, defaults, messages and output files, including --scoreSeqset (.occurrence), --FDR (cross-validated .zoops.stats),
 // --saveLogOdds and --advanceEM (EM::mask); --gpus N shards the sequences (--EM) and spreads the cross-validation folds
-// (--FDR) over N GPUs.  Not ported (exit with a clear message): --CGS, non-STANDARD alphabets.
+// (--FDR) over N GPUs.  --seedKmers w (an extension) needs no model file: the most enriched w-mers of the positives, counted
+// on the device, become OUTDIR/<basename>_seeds.meme, which the run reads like a --PWMFile.  Not ported (exit with a clear message): --CGS, non-STANDARD alphabets.
 // main() is the sequence of stages, in mainBaMM.cpp's order; the stages and the state they share are in driver.h.
 #include <cstdio>
 #include <cstdlib>

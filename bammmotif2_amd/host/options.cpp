@@ -27,7 +27,7 @@ void print_help() {
     printf("\t SEQFILE: file with sequences from positive set in FASTA format\n\n");
     printf("\t OPTIONS (same names and defaults as the reference, Global.cpp:142-341):\n");
     printf("\t\t --basename <STRING> --negSeqFile <FILE> --ss --alphabet STANDARD\n");
-    printf("\t\t --bindingSiteFile <FILE> | --PWMFile <FILE> | --BaMMFile <FILE>   --maxPWM <INT>\n");
+    printf("\t\t --bindingSiteFile <FILE> | --PWMFile <FILE> | --BaMMFile <FILE> | --seedKmers <INT> (extension)   --maxPWM <INT>\n");
     printf("\t\t -k, --order <INT> (2)   -a, --alpha <FLOAT>..   -b, --beta <FLOAT> (7)   -r, --gamma <FLOAT> (3)\n");
     printf("\t\t --extend <INT> [<INT>]   --bgModelFile <FILE>   -K, --Order <INT> (2)   -A, --Alpha <FLOAT>..\n");
     printf("\t\t --EM   -q <FLOAT> (0.3)   --optimizeQ   --verbose   --saveBaMMs   --saveInitialBaMMs\n");
@@ -39,6 +39,9 @@ void print_help() {
     printf("\t\t --hostPvalues (--scoreSeqset: ScoreSeqSet::calcPvalues on downloaded window scores instead of on the device)\n");
     printf("\t\t --hostPositions (--saveBaMMs: .positions from downloaded responsibilities instead of the sites found on the device)\n");
     printf("\t\t --hostFdr (--FDR --mops: the MOPS statistics from downloaded window scores instead of on the device)\n");
+    printf("\t\t --seedKmers <INT> (6..8: no model file; the most enriched w-mers of SEQFILE, counted on the device, seed the run\n");
+    printf("\t\t\t through OUTDIR/<basename>_seeds.meme; --maxPWM defaults to 4 here)\n");
+    printf("\t\t --hostSeedCounts (--seedKmers: the w-mer counts on the host instead of on the device)\n");
     printf("\t\t --gpus <INT> (1)   --deviceList <INT,INT,..>\n");
     printf("\t\t\t --EM: the sequences are sharded over the GPUs, one RCCL all-reduce of the count table per iteration;\n");
     printf("\t\t\t --FDR: cross-validation fold f runs on GPU f mod N (FDR.cpp:37 runs the folds on host threads).\n");
@@ -130,11 +133,26 @@ void parse_reference(Args& a, Options& o) {
     a.get_str(0, "alphabet", o.alphabet);
     o.ss = a.present(0, "ss");
     { std::string tmp; a.get_str(0, "intensityFile", tmp); }
-    if (a.get_str(0, "bindingSiteFile", o.seed_file)) o.seed_tag = "bindingsites";
+    if (a.present(0, "seedKmers")) {
+        // this build's fourth way to give the initial model: the seeds are found in SEQFILE itself and written to
+        // OUTDIR/<basename>_seeds.meme, which the run then reads like any --PWMFile
+        for (const char* file_flag : {"bindingSiteFile", "PWMFile", "BaMMFile"})
+            if (a.longs.count(file_flag)) {
+                fprintf(stderr, "Error: --seedKmers cannot be combined with --%s: give the initial model one way.\n", file_flag);
+                exit(1);
+            }
+        if (!a.get(0, "seedKmers", o.seedKmers) || o.seedKmers < 6 || o.seedKmers > 8) {
+            fprintf(stderr, "Error: --seedKmers takes a width from 6 to 8.\n");
+            exit(1);
+        }
+        o.seed_file = o.out_dir + '/' + o.basename + "_seeds.meme";
+        o.seed_tag = "PWM";
+    }
+    else if (a.get_str(0, "bindingSiteFile", o.seed_file)) o.seed_tag = "bindingsites";
     else if (a.get_str(0, "PWMFile", o.seed_file)) o.seed_tag = "PWM";
     else if (a.get_str(0, "BaMMFile", o.seed_file)) o.seed_tag = "BaMM";
     else { fprintf(stderr, "Error: No initial model is provided.\n"); exit(1); }
-    a.get(0, "maxPWM", o.maxPWM);
+    if (!a.get(0, "maxPWM", o.maxPWM) && o.seedKmers) o.maxPWM = 4;
     o.mops = a.present(0, "mops");
     a.get(0, "zoops", o.zoops);
     a.get('k', "order", o.K);
@@ -207,6 +225,7 @@ void parse_extensions(Args& a, Options& o) {
     o.hostPvalues = a.present(0, "hostPvalues");
     o.hostPositions = a.present(0, "hostPositions");
     o.hostFdr = a.present(0, "hostFdr");
+    o.hostSeedCounts = a.present(0, "hostSeedCounts");
     a.get(0, "gpus", o.gpus);
     {   // --deviceList 0,1,2: explicit devices (a device may appear twice for the fold replicas of --FDR; the
         // sharded --EM wants distinct ones, RCCL has one rank per GPU)

@@ -23,8 +23,9 @@ struct Options {                       // Global.cpp:6-96 defaults
     std::vector<size_t> extend{0, 0};
     size_t cvFold = 4, mFold = 1, sOrder = 2, threads = 4;
     uint32_t max_iter = 1000;
+    uint32_t seedKmers = 0;            // --seedKmers w: seeds from the w-mer counts of the positives (0 = a model file is given)
     int device = 0;
-    bool timing = false, hostSeeding = false, hostPacking = false, hostSampler = false, hostPvalues = false, hostPositions = false, hostFdr = false, forceComm = false, debug = false;
+    bool timing = false, hostSeeding = false, hostPacking = false, hostSampler = false, hostPvalues = false, hostPositions = false, hostFdr = false, hostSeedCounts = false, forceComm = false, debug = false;
     size_t gpus = 1;                   // --gpus N: devices device .. device+N-1 (or --deviceList)
     std::vector<int> device_list;
     bool need_gpu() const { return EM || score || FDR; }

@@ -165,6 +165,10 @@ int  bamm_ctx_set_launch(bamm_ctx* ctx, uint32_t blocks, uint32_t threads_per_bl
  *   "neg_segment_positions" n  bamm_sample_negatives: positions per segment of a negative longer than
  *                       BAMM_MAX_SEQ_POSITIONS (16..2^20, rounded down to a multiple of 16; 0 = the default,
  *                       bamm_neg_segment_geometry); the same negatives whatever the cut; for measurements
+ *   "kmer_segment_positions" n  bamm_kmer_counts: positions per segment of a record longer than that (16..2^20, rounded
+ *                       down to a multiple of 16; 0 = the default, BAMM_MAX_SEQ_POSITIONS); the same table whatever the cut
+ *   "kmer_flush_windows" n  bamm_kmer_counts: a workgroup flushes its LDS table once it has added n windows (0 = the
+ *                       default, 2^31); the same table whatever the threshold; for tests
  * There are no environment variables that change what the library computes or launches.          */
 int  bamm_ctx_set_tuning(bamm_ctx* ctx, const char* key, int value);
 /* Device blocks the library has handed to an owner (a sequence set, a handle, a call's temporaries) and not yet taken
@@ -576,6 +580,33 @@ int  bamm_sample_negatives(bamm_ctx* ctx, bamm_seqs* positives, uint32_t s_order
  * bamm_sample_negatives cuts it unless "neg_segment_positions" is set.  Pure, no device needed: tests use it to place
  * sequence lengths on the cuts.                                                                                   */
 int  bamm_neg_segment_geometry(uint32_t* segment_positions);
+
+/* ------------------------------------------------------------------ w-mer counts -------- */
+/* The exact w-mer table of a resident set, w = 6..8 (anything else: BAMM_ERR_ARG) -- what the de novo seeder of the
+ * BaMMmotif driver ranks (--seedKmers; the reference has no such stage).  In terms of the FASTA codes the set was built
+ * from (0 = unknown, 1..4 = A,C,G,T): every window of w consecutive codes of a record with no 0 in it adds 1 to counts[y],
+ * y = the window read as a base-4 number of the codes minus 1, oldest base most significant (the digit order of kmer_);
+ * unless the set is single-stranded the window's reverse complement adds 1 as well, so a reverse-palindromic window adds
+ * 2 to its own cell.  No window spans the strand separator, and the bases Sequence.cpp:38 draws for unknown positions are
+ * not counted: the table does not depend on the rand() stream.  *n_windows (may be NULL) = the sum of the table.
+ * Records of any length: one beyond BAMM_MAX_SEQ_POSITIONS ("kmer_segment_positions" in bamm_ctx_set_tuning: 16..2^20,
+ * rounded down to a multiple of 16) goes through the same kernel in segments that overlap by w - 1 positions.  The table
+ * is privatised in LDS per workgroup (32-bit cells; at w = 8 two workgroups share a block's records, each with the half of
+ * the table its leading base selects) and flushed into 64-bit cells; a workgroup also flushes after
+ * "kmer_flush_windows" windows (default 2^31), so no LDS cell wraps.  bamm_ctx_set_launch's blocks apply.
+ * The set must know where its unknown bases were: bamm_seqs_upload of a set bamm_pack_codes* made -- the list is noted
+ * beside the packed set, by its address, until bamm_packed_free releases it (release every packed set through that call: a
+ * bamm_packed copied by value has no list, and one freed any other way would leave its note to whatever is allocated at
+ * that address next).  Every other set cannot tell and is refused with BAMM_ERR_UNSUPPORTED: one packed from kmer_ arrays
+ * (bamm_pack_kmers*, the sampled negatives) and, as yet, one bamm_seqs_from_codes packed on the device.  The strand mode
+ * is the one the packed set was made with.                                                                         */
+int  bamm_kmer_counts(bamm_ctx* ctx, const bamm_seqs* seqs, uint32_t w, uint64_t* counts /* [4^w] host */,
+                      uint64_t* n_windows);
+/* The same table from the codes themselves, on the host threads (bamm_set_host_threads): the same integers for codes
+ * 0..4, which is all the FASTA reader produces.  A code above 4 counts as unknown here, while the packers encode it as
+ * (code - 1) mod 4 and list only code 0: the two tables agree on codes 0..4 only.                                  */
+int  bamm_kmer_counts_host(const uint8_t* codes, const uint64_t* off, uint64_t n_seqs, int single_strand, uint32_t w,
+                           uint64_t* counts /* [4^w] */, uint64_t* n_windows);
 
 /* ------------------------------------------------------------------ small host helpers -- */
 /* BackgroundModel ctor + calculateV (BackgroundModel.cpp:3-46, :441-473): interpolated
