@@ -51,7 +51,7 @@ SYMBOLS = [
     "bamm_em_set_allreduce", "bamm_em_set_comm", "bamm_comm_init_all", "bamm_comm_unique_id", "bamm_comm_init_rank",
     "bamm_comm_info", "bamm_comm_destroy", "bamm_comm_time_allreduce", "bamm_em_comm_mode", "bamm_seqs_from_codes", "bamm_seqs_bg_model", "bamm_sample_negatives", "bamm_neg_segment_geometry", "bamm_rand_stream_draws", "bamm_comm_init_local", "bamm_comm_init_shm", "bamm_comm_abort", "bamm_device_count", "bamm_device_pci_bus_id", "bamm_device_can_access_peer", "bamm_em_get_v", "bamm_em_get_counts", "bamm_em_get_s", "bamm_em_get_q",
     "bamm_em_get_llh", "bamm_em_get_vdiff", "bamm_em_get_iteration", "bamm_em_get_r",
-    "bamm_em_get_trace", "bamm_em_kernel_time", "bamm_em_set_kernel_timing", "bamm_em_plan", "bamm_em_plan_mixed", "bamm_em_plan_launch", "bamm_em_plan_paths", "bamm_em_plan_update", "bamm_em_tile_geometry", "bamm_em_tile_plan", "bamm_mask_plan", "bamm_mix_layout", "bamm_mix_fix_word", "bamm_device_blocks_live", "bamm_seed_from_pwm", "bamm_set_host_threads", "bamm_logodds", "bamm_logodds_subset", "bamm_score_tile_geometry", "bamm_score_slice_geometry", "bamm_score_plan", "bamm_occurrences", "bamm_occ_info", "bamm_occ_get", "bamm_occ_destroy", "bamm_em_sites", "bamm_sites_info", "bamm_sites_get", "bamm_sites_best", "bamm_sites_destroy", "bamm_fdr_create", "bamm_fdr_add_set", "bamm_fdr_add_scores", "bamm_fdr_seal", "bamm_fdr_absorb", "bamm_fdr_statistics", "bamm_fdr_info", "bamm_fdr_rows", "bamm_fdr_pvalues", "bamm_fdr_geometry", "bamm_fdr_destroy", "bamm_kmer_counts", "bamm_kmer_counts_host", "bamm_bg_model", "bamm_calculate_p", "bamm_v_size",
+    "bamm_em_get_trace", "bamm_em_kernel_time", "bamm_em_set_kernel_timing", "bamm_em_plan", "bamm_em_plan_mixed", "bamm_em_plan_launch", "bamm_em_plan_paths", "bamm_em_plan_update", "bamm_em_tile_geometry", "bamm_em_tile_plan", "bamm_mask_plan", "bamm_mix_layout", "bamm_mix_fix_word", "bamm_device_blocks_live", "bamm_seed_from_pwm", "bamm_set_host_threads", "bamm_logodds", "bamm_logodds_subset", "bamm_score_tile_geometry", "bamm_score_slice_geometry", "bamm_score_plan", "bamm_occurrences", "bamm_occ_info", "bamm_occ_get", "bamm_occ_destroy", "bamm_em_sites", "bamm_sites_info", "bamm_sites_get", "bamm_sites_best", "bamm_sites_destroy", "bamm_fdr_create", "bamm_fdr_add_set", "bamm_fdr_add_scores", "bamm_fdr_seal", "bamm_fdr_absorb", "bamm_fdr_statistics", "bamm_fdr_info", "bamm_fdr_rows", "bamm_fdr_pvalues", "bamm_fdr_geometry", "bamm_fdr_destroy", "bamm_kmer_counts", "bamm_kmer_counts_host", "bamm_kmer_counts_gapped", "bamm_kmer_counts_gapped_host", "bamm_bg_model", "bamm_calculate_p", "bamm_v_size",
     "bamm_v_offset", "bamm_bg_size",
 ]
 
@@ -174,6 +174,8 @@ def load() -> C.CDLL:
     L.bamm_fdr_destroy.argtypes = [vp]
     L.bamm_kmer_counts.argtypes = [vp, vp, u32, u64p, P(u64)]
     L.bamm_kmer_counts_host.argtypes = [u8p, u64p, u64, i, u32, u64p, P(u64)]
+    L.bamm_kmer_counts_gapped.argtypes = [vp, vp, u32, u32, u32, u64p, u64p]
+    L.bamm_kmer_counts_gapped_host.argtypes = [u8p, u64p, u64, i, u32, u32, u32, u64p, u64p]
     L.bamm_bg_model.argtypes = [P(Packed), u32, f32p, f32p]
     L.bamm_calculate_p.argtypes = [f32p, f32p, u32, u32, u32, f32p]
     for name in ("bamm_v_size", "bamm_v_offset"):

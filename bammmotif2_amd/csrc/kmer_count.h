@@ -17,7 +17,7 @@ struct KmerCountArgs {
     uint32_t seg_words;          // words per segment
     uint32_t single_strand;
     uint32_t flush_windows;      // a workgroup flushes its table once it has added this many windows
-    unsigned long long* counts;  // [4^w], added into
+    unsigned long long* counts;  // [4^w], added into (the gapped launch: [gaps][4^w])
 };
 
 // One launch: `blocks` x `passes` workgroups of `threads`; workgroup (b, h) holds the `cells` cells of the table whose
@@ -25,5 +25,9 @@ struct KmerCountArgs {
 struct KmerLaunch { uint32_t blocks, threads, passes, cells; size_t lds; };
 KmerLaunch kmer_count_geometry(uint32_t w, int num_cus, uint32_t blocks, uint32_t threads);
 int launch_kmer_counts(const KmerCountArgs& a, uint32_t w, const KmerLaunch& g, hipStream_t st);
+// The dyad tables of gaps gap_lo .. gap_lo + n_gaps - 1 (w = 6 or 8, w + the largest gap <= 16) in one launch of
+// `blocks` x `passes` x n_gaps workgroups: workgroup (b, h, z) is workgroup (b, h) of the launch above for the windows whose
+// halves lie gap_lo + z positions apart, and adds into a.counts + z * 4^w.
+int launch_kmer_counts_gapped(const KmerCountArgs& a, uint32_t w, uint32_t gap_lo, uint32_t n_gaps, const KmerLaunch& g, hipStream_t st);
 
 }  // namespace bamm

@@ -28,6 +28,15 @@
 // upper bound of the windows it added (16 per word) to a running total and flushes the table when the total has reached
 // `flush_windows` (at most 2^31).  A round adds fewer than 16 waves x 8 entries x 2^20 positions = 2^27 windows, so no cell
 // exceeds 2^31 + 2^27 between two flushes.
+//
+// Dyads (k_kmer_counts_gapped, w = 6 or 8): a window of span S = w + g <= 16 whose first and last h = w / 2 positions form the
+// cell and whose g positions between them only have to be known.  The same walk, with the grid's z axis over the gaps asked
+// for: workgroup (b, p, z) serves gap gap_lo + z alone and adds into table z, so the bound of 16 windows per word and
+// workgroup, and with it the flush rule, stands as it is.  A lane's own word is bits 16..31 of its 32 positions, so a
+// window that ends there (i >= 16) starts at bit i - S + 1 >= 1: its two halves are two shifts of the same 64-bit
+// register and its validity a run of S bits of the same mask, and the S - 1 positions of overlap between two segments are
+// still the previous word a lane reads anyway -- for the same reason as w - 1 above, which is the case g = 0.  The
+// contiguous kernels take none of this: the gap is a template switch, not a branch on their path.
 #include "kmer_count.h"
 
 namespace bamm {
@@ -87,10 +96,14 @@ __device__ __forceinline__ uint32_t unknown_bits(const Entry& e, int64_t lo, boo
     return bad;
 }
 
-template <int W>
-__device__ __forceinline__ void count_entry(const KmerCountArgs& a, const Entry& e, uint32_t* hist, uint32_t pass, int lane) {
+// kGapped: the window's halves lie `gap` positions apart (the same in every lane of the launch's workgroup)
+template <int W, bool kGapped>
+__device__ __forceinline__ void count_entry(const KmerCountArgs& a, const Entry& e, uint32_t* hist, uint32_t pass, int lane, uint32_t gap) {
     constexpr uint32_t kMask = (1u << (2 * W)) - 1u, kRun = (1u << W) - 1u;
     constexpr uint32_t kCellBits = 2 * W > 15 ? 15 : 2 * W;
+    constexpr uint32_t kHalf = W / 2, kMaskHalf = (1u << W) - 1u;   // (gapped: W is even)
+    const uint32_t span = (uint32_t)W + gap;                  // <= 16
+    const uint32_t run = (1u << span) - 1u;
     const bool ds = a.single_strand == 0u;
     const int64_t L = e.L, L0 = (L - 1) / 2;                  // both strands: L = 2 L0 + 1, the separator at L0
     bool first = true;
@@ -103,34 +116,51 @@ __device__ __forceinline__ void count_entry(const KmerCountArgs& a, const Entry&
         if (ds && L0 >= lo && L0 < lo + 32) bad |= 1u << (uint32_t)(L0 - lo);
         if (e.nu) bad |= unknown_bits(e, lo, ds, L0);
         const unsigned long long both = ((unsigned long long)prev << 32) | cur;
+        if constexpr (!kGapped) {
 #pragma unroll
-        for (int i = 16; i < 32; i++) {                       // the window that ends at position lo + i
-            const bool ok = ((bad >> (i - W + 1)) & kRun) == 0u;
-            const uint32_t y = (uint32_t)(both >> (62 - 2 * i)) & kMask;
-            if (ok && (y >> kCellBits) == pass) atomicAdd(&hist[y & ((1u << kCellBits) - 1u)], 1u);
+            for (int i = 16; i < 32; i++) {                   // the window that ends at position lo + i
+                const bool ok = ((bad >> (i - W + 1)) & kRun) == 0u;
+                const uint32_t y = (uint32_t)(both >> (62 - 2 * i)) & kMask;
+                if (ok && (y >> kCellBits) == pass) atomicAdd(&hist[y & ((1u << kCellBits) - 1u)], 1u);
+            }
+        } else {
+            // the left half ends h + gap positions before the window does, and the span starts at bit i - span + 1 >= 1: both as
+            // one shift per word by what depends on the gap, then the constant shifts of the contiguous case
+            const unsigned long long lefts = both >> (2u * (kHalf + gap));
+            const uint32_t bads = bad >> (16u - span);
+#pragma unroll
+            for (int i = 16; i < 32; i++) {                   // the window that ends at position lo + i
+                const bool ok = ((bads >> (i - 15)) & run) == 0u;
+                const uint32_t right = (uint32_t)(both >> (62 - 2 * i)) & kMaskHalf;
+                const uint32_t left = (uint32_t)(lefts >> (62 - 2 * i)) & kMaskHalf;
+                const uint32_t y = (left << W) | right;
+                if (ok && (y >> kCellBits) == pass) atomicAdd(&hist[y & ((1u << kCellBits) - 1u)], 1u);
+            }
         }
     }
 }
 
-template <int W>
-__global__ void __launch_bounds__(1024) k_kmer_counts(KmerCountArgs a) {
+// the walk of workgroup (blockIdx.x, blockIdx.y) of `threads` threads over the records, into `table` [4^W] (the kernel reads
+// its own blockDim: only there does the compiler know the workgroups of a launch to be of one size)
+template <int W, bool kGapped>
+__device__ __forceinline__ void count_records(const KmerCountArgs& a, unsigned long long* table, uint32_t gap, const uint32_t threads) {
     extern __shared__ uint32_t kmer_lds[];                    // [cells] the table, [1] windows added since the last flush (upper bound)
     constexpr uint32_t kCells = 2 * W > 15 ? (1u << 15) : (1u << (2 * W));
     uint32_t* hist = kmer_lds;
     uint32_t* added_total = kmer_lds + kCells;
     const uint32_t pass = blockIdx.y;
-    unsigned long long* out = a.counts + (size_t)pass * kCells;
-    for (uint32_t i = threadIdx.x; i < kCells; i += blockDim.x) hist[i] = 0u;
+    unsigned long long* out = table + (size_t)pass * kCells;
+    for (uint32_t i = threadIdx.x; i < kCells; i += threads) hist[i] = 0u;
     if (threadIdx.x == 0) *added_total = 0u;
     __syncthreads();
     auto flush = [&]() {                                      // every cell belongs to one thread
-        for (uint32_t i = threadIdx.x; i < kCells; i += blockDim.x) {
+        for (uint32_t i = threadIdx.x; i < kCells; i += threads) {
             const uint32_t v = hist[i];
             if (v) { atomicAdd(&out[i], (unsigned long long)v); hist[i] = 0u; }
         }
     };
     const int lane = threadIdx.x & 63;
-    const uint32_t wave = threadIdx.x >> 6, waves = blockDim.x >> 6;
+    const uint32_t wave = threadIdx.x >> 6, waves = threads >> 6;
     const uint64_t total = a.n + a.n_items;
     const uint64_t per_round = (uint64_t)waves * kEntriesPerRound;
     for (uint64_t base = (uint64_t)blockIdx.x * per_round; base < total; base += (uint64_t)gridDim.x * per_round) {   // (the same trip count for every wave of the block)
@@ -141,7 +171,7 @@ __global__ void __launch_bounds__(1024) k_kmer_counts(KmerCountArgs a) {
             const Entry cur = nxt;
             if (r + 1u < kEntriesPerRound) nxt = fetch_entry(a, t0 + r + 1u, total, lane);
             added += (cur.we - cur.wb) * 16u;
-            count_entry<W>(a, cur, hist, pass, lane);
+            count_entry<W, kGapped>(a, cur, hist, pass, lane, gap);
         }
         if (lane == 0 && added) atomicAdd(added_total, added);
         __syncthreads();
@@ -154,6 +184,17 @@ __global__ void __launch_bounds__(1024) k_kmer_counts(KmerCountArgs a) {
         }
     }
     flush();
+}
+
+template <int W>
+__global__ void __launch_bounds__(1024) k_kmer_counts(KmerCountArgs a) {
+    count_records<W, false>(a, a.counts, 0u, blockDim.x);
+}
+
+// workgroup (b, p, z): the walk of (b, p) for gap gap_lo + z, into table z of a.counts [gaps][4^W]
+template <int W>
+__global__ void __launch_bounds__(1024) k_kmer_counts_gapped(KmerCountArgs a, uint32_t gap_lo) {
+    count_records<W, true>(a, a.counts + ((size_t)blockIdx.z << (2 * W)), gap_lo + blockIdx.z, blockDim.x);
 }
 
 }  // namespace
@@ -183,6 +224,25 @@ int launch_kmer_counts(const KmerCountArgs& a, uint32_t w, const KmerLaunch& g, 
         case 8: return go(k_kmer_counts<8>);
     }
     set_error("launch_kmer_counts: w = %u outside 6..8", w);
+    return BAMM_ERR_ARG;
+}
+
+int launch_kmer_counts_gapped(const KmerCountArgs& a, uint32_t w, uint32_t gap_lo, uint32_t n_gaps, const KmerLaunch& g, hipStream_t st) {
+    if (n_gaps == 0u || w + gap_lo + n_gaps - 1u > 16u) {     // (the kernel's shifts rest on span <= 16)
+        set_error("launch_kmer_counts_gapped: gaps %u..%u leave the span of 16 at w = %u", gap_lo, gap_lo + n_gaps - 1u, w);
+        return BAMM_ERR_ARG;
+    }
+    auto go = [&](auto kernel) -> int {
+        if (int rc = allow_lds(reinterpret_cast<const void*>(kernel), g.lds)) return rc;
+        hipLaunchKernelGGL(kernel, dim3(g.blocks, g.passes, n_gaps), dim3(g.threads), g.lds, st, a, gap_lo);
+        BAMM_HIP(hipGetLastError());
+        return BAMM_OK;
+    };
+    switch (w) {
+        case 6: return go(k_kmer_counts_gapped<6>);
+        case 8: return go(k_kmer_counts_gapped<8>);
+    }
+    set_error("launch_kmer_counts_gapped: w = %u is neither 6 nor 8", w);
     return BAMM_ERR_ARG;
 }
 

@@ -617,4 +617,48 @@ int bamm_kmer_counts_host(const uint8_t* codes, const uint64_t* off, uint64_t n_
     return BAMM_OK;
 }
 
+// The host twin of bamm_kmer_counts_gapped: per record the last 16 bases and their reverse complement as two rolling 32-bit
+// registers, from which every gap's window that ends at the position is two shifts; ranges of records on the host threads
+// with a set of tables each, summed at the end.
+int bamm_kmer_counts_gapped_host(const uint8_t* codes, const uint64_t* off, uint64_t n_seqs, int single_strand, uint32_t w,
+                                 uint32_t gap_lo, uint32_t gap_hi, uint64_t* counts, uint64_t* n_windows) {
+    if (!counts || (n_seqs && (!codes || !off))) { set_error("bamm_kmer_counts_gapped_host: null argument"); return BAMM_ERR_ARG; }
+    if (int rc = kmer_gap_range_ok("bamm_kmer_counts_gapped_host", w, gap_lo, gap_hi)) return rc;
+    const size_t cells = ipow4(w), n_gaps = gap_hi - gap_lo + 1u, all = cells * n_gaps;
+    // the halves: the last w - h bases and the h bases `gap` positions before them (w = 7 comes with gap 0 only: 3 + 4)
+    const uint32_t h = w / 2u, hr = w - h, mask_l = (1u << (2u * h)) - 1u, mask_r = (1u << (2u * hr)) - 1u;
+    const uint32_t T = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(host_threads(), n_seqs / 1024 + 1));
+    std::vector<std::vector<uint64_t>> part(T, std::vector<uint64_t>(all, 0));
+    parallel_ranges(n_seqs, T, [&](uint32_t t, uint64_t n0, uint64_t n1) {
+        for (uint64_t n = n0; n < n1; n++) {
+            uint32_t fwd = 0, rev = 0, run = 0;              // fwd: the newest base in bits 0..1; rev: its complement in bits 30..31; run: codes since the last unknown one
+            for (uint64_t i = off[n]; i < off[n + 1]; i++) {
+                const uint32_t c = codes[i];
+                if (c < 1u || c > 4u) { run = 0; continue; }
+                fwd = (fwd << 2) | (c - 1u);
+                rev = (rev >> 2) | ((4u - c) << 30);
+                run++;
+                for (uint32_t g = gap_lo; g <= gap_hi && w + g <= run; g++) {
+                    uint64_t* mine = part[t].data() + (g - gap_lo) * cells;
+                    const uint32_t span = w + g;
+                    mine[(((fwd >> (2u * (hr + g))) & mask_l) << (2u * hr)) | (fwd & mask_r)]++;
+                    // the reverse complement's leading hr bases are the complements of the newest ones, its last h those of the window's first
+                    if (!single_strand) mine[(((rev >> (32u - 2u * hr)) & mask_r) << (2u * h)) | ((rev >> (32u - 2u * span)) & mask_l)]++;
+                }
+            }
+        }
+    });
+    for (size_t z = 0; z < n_gaps; z++) {
+        uint64_t total = 0;
+        for (size_t y = 0; y < cells; y++) {
+            uint64_t c = 0;
+            for (uint32_t t = 0; t < T; t++) c += part[t][z * cells + y];
+            counts[z * cells + y] = c;
+            total += c;
+        }
+        if (n_windows) n_windows[z] = total;
+    }
+    return BAMM_OK;
+}
+
 }  // extern "C"

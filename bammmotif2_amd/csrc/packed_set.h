@@ -58,6 +58,16 @@ void packed_note_unknowns(const bamm_packed* p, std::shared_ptr<const UnknownLis
 std::shared_ptr<const UnknownList> packed_unknowns(const bamm_packed* p);                  // null: none noted
 void packed_forget_unknowns(const bamm_packed* p);
 
+// What bamm_kmer_counts_gapped and its host twin accept (include/bamm_em.h): w = 6..8, gap_lo <= gap_hi, span w + gap_hi <= 16,
+// and a gap above 0 only between equal halves (w even).
+inline int kmer_gap_range_ok(const char* who, uint32_t w, uint32_t gap_lo, uint32_t gap_hi) {
+    if (w < 6 || w > 8) { set_error("%s: w = %u outside 6..8", who, w); return BAMM_ERR_ARG; }
+    if (gap_lo > gap_hi) { set_error("%s: gap_lo = %u above gap_hi = %u", who, gap_lo, gap_hi); return BAMM_ERR_ARG; }
+    if (gap_hi > 16u - w) { set_error("%s: w + gap_hi = %u + %u exceeds the span of 16", who, w, gap_hi); return BAMM_ERR_ARG; }
+    if ((w & 1u) && gap_hi > 0) { set_error("%s: a gap needs equal halves, w = %u is odd", who, w); return BAMM_ERR_ARG; }
+    return BAMM_OK;
+}
+
 // The length rule: 16 positions per 32-bit word, every sequence on a word boundary.  From p->n_seqs lengths (`lens` may
 // be p->len itself) it fills len, word_off, n_words, total_len, max_len and min_len (0 for an empty set).  exc_off is
 // left as it is: all zero as allocated, which is right for a set given by its lengths alone (no exceptions).  On a bare

@@ -655,6 +655,52 @@ def kmer_seeds(counts, n_windows: int, vbg, Kbg: int, w: int, max_seeds: int = 4
     return kmer[: n.value].copy(), z[: n.value].copy(), pwm[: n.value].copy()
 
 
+def _gapped_tables(w: int, gap_lo: int, gap_hi: int):
+    """Zeroed (counts [n_gaps, 4^w], n_windows [n_gaps]) for a range the library accepts; a 1 x 1 table for one it will refuse."""
+    ok = 6 <= int(w) <= 8 and 0 <= int(gap_lo) <= int(gap_hi) <= 16 - int(w)
+    n_gaps = int(gap_hi) - int(gap_lo) + 1 if ok else 1
+    return np.zeros((n_gaps, 4 ** int(w) if ok else 1), np.uint64), np.zeros(n_gaps, np.uint64)
+
+
+def kmer_counts_gapped(ctx: Context, seqs: SeqSet, w: int, gap_lo: int, gap_hi: int):
+    """The dyad tables of a resident set built from codes (bamm_kmer_counts_gapped), w = 6 or 8, gaps gap_lo..gap_hi with
+    w + gap_hi <= 16, in one launch: (counts uint64 [n_gaps, 4^w], n_windows uint64 [n_gaps]).  A cell is the window's first
+    and last w / 2 bases as one base-4 number, oldest base most significant; gap 0 is kmer_counts' table."""
+    counts, totals = _gapped_tables(w, gap_lo, gap_hi)
+    check(ctx.lib.bamm_kmer_counts_gapped(ctx.h, seqs.h, int(w) & 0xffffffff, int(gap_lo) & 0xffffffff, int(gap_hi) & 0xffffffff, counts.reshape(-1), totals))
+    return counts, totals
+
+
+def kmer_counts_gapped_host(codes, off, w: int, gap_lo: int, gap_hi: int, single_strand: bool = False):
+    """The same tables from the FASTA codes, on the host threads (bamm_kmer_counts_gapped_host)."""
+    off = _u64(off)
+    counts, totals = _gapped_tables(w, gap_lo, gap_hi)
+    check(abi.load().bamm_kmer_counts_gapped_host(np.ascontiguousarray(codes, np.uint8), off, len(off) - 1, int(single_strand), int(w) & 0xffffffff,
+                                                  int(gap_lo) & 0xffffffff, int(gap_hi) & 0xffffffff, counts.reshape(-1), totals))
+    return counts, totals
+
+
+def kmer_seeds_gapped(counts, n_windows, vbg, Kbg: int, w: int, gap_lo: int, gap_hi: int, max_seeds: int = 4, single_strand: bool = False):
+    """The seeds the BaMMmotif driver takes from the dyad tables of gaps gap_lo..gap_hi under --seedKmers --seedGaps
+    (host/seeder.cpp, kmer_seeds_gapped): (w-mers uint32 [n], gaps uint32 [n], z-scores float64 [n], a list of n PWMs
+    float32 [4][w + gap]) in rank order."""
+    H = _host()
+    counts, totals, vbg = _u64(counts).reshape(-1), _u64(n_windows).reshape(-1), _f32(vbg)
+    n_gaps = gap_hi - gap_lo + 1
+    assert len(counts) == n_gaps * 4 ** w and len(totals) == n_gaps and len(vbg) >= bg_size(Kbg)
+    cap = max(int(max_seeds), 1)
+    n = C.c_uint32(0)
+    kmer, gap, cnt, z = np.zeros(cap, np.uint32), np.zeros(cap, np.uint32), np.zeros(cap, np.uint64), np.zeros(cap, np.float64)
+    pwm = np.zeros((cap, 4 * (w + gap_hi)), np.float32)
+    vp = lambda a: a.ctypes.data_as(C.c_void_p)
+    if H.bh_kmer_seeds_gapped(vp(counts), vp(totals), C.c_uint32(w), C.c_uint32(gap_lo), C.c_uint32(gap_hi), C.c_uint32(Kbg), vp(vbg),
+                              C.c_uint64(int(max_seeds)), C.c_int(int(single_strand)), C.byref(n), vp(kmer), vp(gap), vp(cnt), vp(z), vp(pwm)):
+        raise RuntimeError(H.bh_last_error().decode(errors="replace"))
+    k = n.value
+    return (kmer[:k].copy(), gap[:k].copy(), z[:k].copy(),
+            [pwm[i, : 4 * (w + int(gap[i]))].reshape(4, w + int(gap[i])).copy() for i in range(k)])
+
+
 def seed_from_pwm(ctx: Context, seqs: SeqSet, K: int, W: int, score, q: float, u):
     """The pass over the sequences of Motif::initFromPWM (Motif.cpp:228-311) on the device: returns
     (counts[v_size(K,W)] int32, z[n_seqs] uint32).  score: [4][W] floored PWM / 0th-order background;

@@ -102,13 +102,27 @@ struct KmerSeed {
     uint32_t kmer = 0;
     uint64_t count = 0;
     double z = 0;
-    std::vector<float> pwm;             // [4][w], pwm[b * w + j]
+    std::vector<float> pwm;             // [4][w + gap], pwm[b * (w + gap) + j]
+    uint32_t gap = 0;                   // positions between the two halves of the w-mer (kmer_seeds_gapped; 0: contiguous)
 };
 void kmer_seeds(const uint64_t* counts, uint64_t n_windows, uint32_t w, const BgModel& bg, size_t max_seeds, bool ss,
                 std::vector<KmerSeed>& out);
 std::string kmer_string(uint32_t kmer, uint32_t w);
+// Dyads (--seedGaps): the tables of gaps gap_lo..gap_hi, counts[gap - gap_lo][4^w] and n_windows[gap - gap_lo] as
+// bamm_kmer_counts_gapped gives them (w even when gap_hi > 0; a cell = the two halves of h = w / 2 bases as one w-mer).
+//   P(y)  at gap 0 as above; at a gap P(left half) P(right half), each an h-mer of its own (the right half starts at order 0)
+//   E, z  as above with the gap's own n_windows
+// All (gap, cell) candidates are visited in descending z (ties: the smaller gap, then the smaller cell).  One is skipped when
+// a seed taken at the SAME gap is within Hamming distance 1 of it or -- both strands -- of its reverse complement (the rule
+// above), or when a seed taken at ANOTHER gap has the same left half or the same right half as it or -- both strands -- as
+// its reverse complement: a dyad leaves shifted copies of itself at the neighbouring gaps (TGACnnnGGCA beside
+// TGACnnnnGCAT), which are one motif.  A seed's PWM has w + gap columns: the w informative ones from the neighbourhood formula
+// above on that gap's table, the gap's columns 0.25 each.
+void kmer_seeds_gapped(const uint64_t* counts, const uint64_t* n_windows, uint32_t w, uint32_t gap_lo, uint32_t gap_hi,
+                       const BgModel& bg, size_t max_seeds, bool ss, std::vector<KmerSeed>& out);
+std::string kmer_string(uint32_t kmer, uint32_t w, uint32_t gap);   // the halves with gap x 'n' between them: TGACnnnnGCAT
 // the seeds as a MEME file load_seeds(tag "PWM") reads back to the same floats: one motif per seed, the w-mer, its count
-// and its z-score in the motif's name line
+// and its z-score in the motif's name line; a dyad with its gap as 'n's in the name, w= w + gap and " gap= g" behind the z-score
 int kmer_seeds_write(const std::string& path, uint32_t w, const std::vector<KmerSeed>& seeds, std::string& err);
 
 // =============================================== negatives ==============================================

@@ -127,12 +127,39 @@ void background_model(Run& run, bamm_seqs* dseqs_all) {
     run.stage("background model");
 }
 
+// --seedGaps: the same with the dyad tables of every gap asked for beside the contiguous one (one launch on the device), ranked
+// together: a seed's PWM spans its gap, and the seed file carries it at that width.
+void dyad_seed_file(Run& run, bamm_seqs*& dseqs_all) {
+    const Options& o = run.o;
+    const uint32_t w = o.seedKmers, lo = o.seedGapLo, hi = o.seedGapHi;
+    const std::string gaps = "gaps " + std::to_string(lo) + ".." + std::to_string(hi);
+    std::vector<uint64_t> counts((size_t(1) << (2 * w)) * (hi - lo + 1)), n_windows(hi - lo + 1, 0);
+    if (o.need_gpu() && !o.hostSeedCounts) {
+        run.make_ctx(run.devs[0]);
+        if (!dseqs_all && bamm_seqs_upload(run.devs[0].ctx, run.packed, 0, run.packed->n_seqs, &dseqs_all)) die_abi("upload");
+        if (bamm_kmer_counts_gapped(run.devs[0].ctx, dseqs_all, w, lo, hi, counts.data(), n_windows.data())) die_abi("dyad counts");
+        run.stage(("dyad counts on the device (--seedKmers --seedGaps, " + gaps + ")").c_str());
+    } else {
+        if (bamm_kmer_counts_gapped_host(run.pos.codes.data(), run.pos.off.data(), run.pos.size(), o.ss ? 1 : 0, w, lo, hi, counts.data(), n_windows.data())) die_abi("dyad counts");
+        run.stage(("dyad counts on the host (--seedKmers --seedGaps, " + gaps + ")").c_str());
+    }
+    std::vector<KmerSeed> seeds;
+    std::string err;
+    kmer_seeds_gapped(counts.data(), n_windows.data(), w, lo, hi, run.bg, o.maxPWM, o.ss, seeds);
+    if (seeds.empty()) die("Error: --seedKmers found no " + std::to_string(w) + "-mer with " + gaps + " that is more frequent than the background model expects.");
+    if (kmer_seeds_write(o.seed_file, w, seeds, err)) die(err);
+    if (o.verbose)
+        for (const KmerSeed& s : seeds) std::cout << "seed " << kmer_string(s.kmer, w, s.gap) << "  count " << s.count << "  z " << s.z << std::endl;
+    run.stage(("rank dyads (" + gaps + "), write the seed file").c_str());
+}
+
 // --seedKmers: the exact w-mer table of the positives (on the device over the resident set, or with --hostSeedCounts / without
 // a GPU stage on the host threads: the same integers), ranked against the background model (seeder.cpp), written as
 // OUTDIR/<basename>_seeds.meme.  seed_models() then reads that file like any --PWMFile: there is no second seeding path.
 void kmer_seed_file(Run& run, bamm_seqs*& dseqs_all) {
     const Options& o = run.o;
     const uint32_t w = o.seedKmers;
+    if (o.seedGaps) return dyad_seed_file(run, dseqs_all);
     std::vector<uint64_t> counts(size_t(1) << (2 * w));
     uint64_t n_windows = 0;
     if (o.need_gpu() && !o.hostSeedCounts) {

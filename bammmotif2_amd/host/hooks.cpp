@@ -149,6 +149,35 @@ int bh_kmer_seeds_write(const char* path, uint32_t w, uint32_t n, const uint32_t
     return kmer_seeds_write(path, w, seeds, g_err);
 }
 
+// kmer_seeds_gapped on caller-provided tables: as bh_kmer_seeds, with gap[max_seeds] and pwm max_seeds x [4][w + gap_hi]
+// (seed i's [4][w + gap[i]] at the start of its slot)
+int bh_kmer_seeds_gapped(const uint64_t* counts, const uint64_t* n_windows, uint32_t w, uint32_t gap_lo, uint32_t gap_hi, uint32_t bg_order,
+                         const float* vbg, uint64_t max_seeds, int ss, uint32_t* n_out, uint32_t* kmer, uint32_t* gap, uint64_t* count,
+                         double* z, float* pwm) {
+    if (w < 6 || w > 8 || gap_lo > gap_hi || w + gap_hi > 16 || ((w & 1u) && gap_hi)) { g_err = "bh_kmer_seeds_gapped: bad w or gaps"; return 1; }
+    std::vector<KmerSeed> seeds;
+    kmer_seeds_gapped(counts, n_windows, w, gap_lo, gap_hi, bg_from(bg_order, vbg), (size_t)max_seeds, ss != 0, seeds);
+    *n_out = (uint32_t)seeds.size();
+    for (size_t i = 0; i < seeds.size(); i++) {
+        kmer[i] = seeds[i].kmer; gap[i] = seeds[i].gap; count[i] = seeds[i].count; z[i] = seeds[i].z;
+        memcpy(pwm + i * 4 * (size_t)(w + gap_hi), seeds[i].pwm.data(), seeds[i].pwm.size() * sizeof(float));
+    }
+    return 0;
+}
+
+// kmer_seeds_write for seeds with gaps: pwm as bh_kmer_seeds_gapped lays it out, slots of [4][w + max_gap]
+int bh_kmer_seeds_write_gapped(const char* path, uint32_t w, uint32_t max_gap, uint32_t n, const uint32_t* kmer, const uint32_t* gap,
+                               const uint64_t* count, const double* z, const float* pwm) {
+    std::vector<KmerSeed> seeds(n);
+    for (uint32_t i = 0; i < n; i++) {
+        if (gap[i] > max_gap) { g_err = "bh_kmer_seeds_write_gapped: a gap above max_gap"; return 1; }
+        seeds[i].kmer = kmer[i]; seeds[i].gap = gap[i]; seeds[i].count = count[i]; seeds[i].z = z[i];
+        const float* at = pwm + i * 4 * (size_t)(w + max_gap);
+        seeds[i].pwm.assign(at, at + 4 * (size_t)(w + gap[i]));
+    }
+    return kmer_seeds_write(path, w, seeds, g_err);
+}
+
 // the MEME reader of load_seeds on its own: motif `index` of the file as [4][*w_out] floats; *n_motifs = motifs in the file
 int bh_read_meme_pwm(const char* path, uint32_t index, uint32_t* n_motifs, uint32_t* w_out, float* pwm_out, uint64_t pwm_cap) {
     uint32_t seen = 0;

@@ -3,7 +3,8 @@
 // flags, defaults, messages and output files, including --scoreSeqset (.occurrence), --FDR (cross-validated .zoops.stats),
 // --saveLogOdds and --advanceEM (EM::mask); --gpus N shards the sequences (--EM) and spreads the cross-validation folds
 // (--FDR) over N GPUs.  --seedKmers w (an extension) needs no model file: the most enriched w-mers of the positives, counted
-// on the device, become OUTDIR/<basename>_seeds.meme, which the run reads like a --PWMFile.  Not ported (exit with a clear message): --CGS, non-STANDARD alphabets.
+// on the device, become OUTDIR/<basename>_seeds.meme, which the run reads like a --PWMFile (--seedGaps: dyads as well, the w-mer's
+// halves up to 16 - w positions apart).  Not ported (exit with a clear message): --CGS, non-STANDARD alphabets.
 // main() is the sequence of stages, in mainBaMM.cpp's order; the stages and the state they share are in driver.h.
 #include <cstdio>
 #include <cstdlib>

@@ -41,6 +41,8 @@ void print_help() {
     printf("\t\t --hostFdr (--FDR --mops: the MOPS statistics from downloaded window scores instead of on the device)\n");
     printf("\t\t --seedKmers <INT> (6..8: no model file; the most enriched w-mers of SEQFILE, counted on the device, seed the run\n");
     printf("\t\t\t through OUTDIR/<basename>_seeds.meme; --maxPWM defaults to 4 here)\n");
+    printf("\t\t --seedGaps <INT> [<INT>] (--seedKmers 6 or 8: dyads as well -- the two halves of the w-mer G positions apart, any bases\n");
+    printf("\t\t\t between them; one value: gaps 0..G, two: lo..hi; w + gap <= 16.  A seed's PWM spans its gap: TGACnnnnGCAT)\n");
     printf("\t\t --hostSeedCounts (--seedKmers: the w-mer counts on the host instead of on the device)\n");
     printf("\t\t --gpus <INT> (1)   --deviceList <INT,INT,..>\n");
     printf("\t\t\t --EM: the sequences are sharded over the GPUs, one RCCL all-reduce of the count table per iteration;\n");
@@ -133,6 +135,10 @@ void parse_reference(Args& a, Options& o) {
     a.get_str(0, "alphabet", o.alphabet);
     o.ss = a.present(0, "ss");
     { std::string tmp; a.get_str(0, "intensityFile", tmp); }
+    if (a.present(0, "seedGaps") && !a.longs.count("seedKmers")) {
+        fprintf(stderr, "Error: --seedGaps needs --seedKmers 6 or 8.\n");
+        exit(1);
+    }
     if (a.present(0, "seedKmers")) {
         // this build's fourth way to give the initial model: the seeds are found in SEQFILE itself and written to
         // OUTDIR/<basename>_seeds.meme, which the run then reads like any --PWMFile
@@ -144,6 +150,18 @@ void parse_reference(Args& a, Options& o) {
         if (!a.get(0, "seedKmers", o.seedKmers) || o.seedKmers < 6 || o.seedKmers > 8) {
             fprintf(stderr, "Error: --seedKmers takes a width from 6 to 8.\n");
             exit(1);
+        }
+        if (a.present(0, "seedGaps")) {
+            // dyads: one value G means the gaps 0..G, two mean lo..hi
+            std::vector<uint32_t> gaps;
+            a.get_vec(0, "seedGaps", gaps);
+            if (o.seedKmers == 7) { fprintf(stderr, "Error: --seedGaps needs --seedKmers 6 or 8.\n"); exit(1); }
+            if (gaps.empty() || gaps.size() > 2 || gaps.size() != a.longs["seedGaps"].size()) { fprintf(stderr, "Error: --seedGaps takes one or two gaps.\n"); exit(1); }
+            o.seedGaps = true;
+            o.seedGapLo = gaps.size() == 2 ? gaps[0] : 0;
+            o.seedGapHi = gaps.back();
+            if (o.seedGapHi > 16 - o.seedKmers || o.seedGapLo > 16 - o.seedKmers) { fprintf(stderr, "Error: --seedGaps: w + gap may not exceed 16.\n"); exit(1); }
+            if (o.seedGapLo > o.seedGapHi) { fprintf(stderr, "Error: --seedGaps: the first gap may not exceed the second.\n"); exit(1); }
         }
         o.seed_file = o.out_dir + '/' + o.basename + "_seeds.meme";
         o.seed_tag = "PWM";

@@ -24,6 +24,8 @@ struct Options {                       // Global.cpp:6-96 defaults
     size_t cvFold = 4, mFold = 1, sOrder = 2, threads = 4;
     uint32_t max_iter = 1000;
     uint32_t seedKmers = 0;            // --seedKmers w: seeds from the w-mer counts of the positives (0 = a model file is given)
+    bool seedGaps = false;             // --seedGaps [lo] hi: dyads as well, the halves of the w-mer seedGapLo..seedGapHi positions apart
+    uint32_t seedGapLo = 0, seedGapHi = 0;
     int device = 0;
     bool timing = false, hostSeeding = false, hostPacking = false, hostSampler = false, hostPvalues = false, hostPositions = false, hostFdr = false, hostSeedCounts = false, forceComm = false, debug = false;
     size_t gpus = 1;                   // --gpus N: devices device .. device+N-1 (or --deviceList)

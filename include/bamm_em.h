@@ -165,9 +165,9 @@ int  bamm_ctx_set_launch(bamm_ctx* ctx, uint32_t blocks, uint32_t threads_per_bl
  *   "neg_segment_positions" n  bamm_sample_negatives: positions per segment of a negative longer than
  *                       BAMM_MAX_SEQ_POSITIONS (16..2^20, rounded down to a multiple of 16; 0 = the default,
  *                       bamm_neg_segment_geometry); the same negatives whatever the cut; for measurements
- *   "kmer_segment_positions" n  bamm_kmer_counts: positions per segment of a record longer than that (16..2^20, rounded
+ *   "kmer_segment_positions" n  bamm_kmer_counts[_gapped]: positions per segment of a record longer than that (16..2^20, rounded
  *                       down to a multiple of 16; 0 = the default, BAMM_MAX_SEQ_POSITIONS); the same table whatever the cut
- *   "kmer_flush_windows" n  bamm_kmer_counts: a workgroup flushes its LDS table once it has added n windows (0 = the
+ *   "kmer_flush_windows" n  bamm_kmer_counts[_gapped]: a workgroup flushes its LDS table once it has added n windows (0 = the
  *                       default, 2^31); the same table whatever the threshold; for tests
  * There are no environment variables that change what the library computes or launches.          */
 int  bamm_ctx_set_tuning(bamm_ctx* ctx, const char* key, int value);
@@ -607,6 +607,25 @@ int  bamm_kmer_counts(bamm_ctx* ctx, const bamm_seqs* seqs, uint32_t w, uint64_t
  * (code - 1) mod 4 and list only code 0: the two tables agree on codes 0..4 only.                                  */
 int  bamm_kmer_counts_host(const uint8_t* codes, const uint64_t* off, uint64_t n_seqs, int single_strand, uint32_t w,
                            uint64_t* counts /* [4^w] */, uint64_t* n_windows);
+/* Dyad tables: w-mers whose two halves lie apart (--seedGaps).  For even w in {6, 8}, half h = w / 2, gap g >= 0 and span
+ * S = w + g <= 16 (g <= 10 at w = 6, g <= 8 at w = 8): every window of S consecutive codes of a record with no 0 ANYWHERE in
+ * the span, the g gap positions included, adds 1 to counts[g - gap_lo][y], y = the window's first h codes followed by its
+ * last h codes (minus 1 each) read as a base-4 number, oldest base most significant.  Unless the set is single-stranded the
+ * window's reverse complement adds 1 as well: with equal halves that is an (h, g, h) window again, so the table of every gap
+ * is its own reverse complement and a reverse-palindromic dyad adds 2 to its own cell.  No window spans the strand
+ * separator, and the bases drawn for unknown positions are never counted.  g = 0 is bamm_kmer_counts' table exactly (w = 7
+ * is accepted with gap_lo = gap_hi = 0 only).  The tables of gaps gap_lo..gap_hi come from ONE launch whose grid has the
+ * gaps as its third axis; n_windows[g - gap_lo] (may be NULL) = the sum of that gap's table.  BAMM_ERR_ARG: gap_lo > gap_hi,
+ * w + gap_hi > 16, odd w with gap_hi > 0 (unequal halves would not map onto themselves under reverse complement), w
+ * outside 6..8, a set of another context; BAMM_ERR_UNSUPPORTED: a set without a list of unknown positions, as above.  An
+ * empty set gives zeroed tables.  "kmer_segment_positions" (segments overlap by S - 1 <= 15 positions: still the one word a
+ * lane reads before its own), "kmer_flush_windows" and bamm_ctx_set_launch's blocks apply as they do above.        */
+int  bamm_kmer_counts_gapped(bamm_ctx* ctx, const bamm_seqs* seqs, uint32_t w, uint32_t gap_lo, uint32_t gap_hi,
+                             uint64_t* counts /* [(gap_hi-gap_lo+1) * 4^w] host */,
+                             uint64_t* n_windows /* [gap_hi-gap_lo+1] or NULL */);
+/* The same tables from the codes, on the host threads: the same integers for codes 0..4.                           */
+int  bamm_kmer_counts_gapped_host(const uint8_t* codes, const uint64_t* off, uint64_t n_seqs, int single_strand,
+                                  uint32_t w, uint32_t gap_lo, uint32_t gap_hi, uint64_t* counts, uint64_t* n_windows);
 
 /* ------------------------------------------------------------------ small host helpers -- */
 /* BackgroundModel ctor + calculateV (BackgroundModel.cpp:3-46, :441-473): interpolated
